@@ -15,6 +15,13 @@ named config, so the reported seq/s is conservative w.r.t. it.
 
 Launch: python bench.py --gpus N --steps K --warmup W
 (N>1 comes via torch.distributed.run; RANK/LOCAL_RANK/WORLD_SIZE env.)
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON
+result line (`ms_per_step` = milliseconds per timed step). `--dump-outputs
+DIR` additionally writes what the last timed step computed as
+DIR/<name>.npy; inputs and initial weights depend only on `--seed`, so two
+builds can be compared output for output. `--full` is reserved for
+measurements beyond the headline figure.
 """
 
 from __future__ import annotations
@@ -94,7 +101,79 @@ def parse_args():
                         "pattern (avoids pure_bf16's per-call grad "
                         "downcasts). fp32 LAMB masters for the bf16 params.")
     p.add_argument("--seed", type=int, default=1234)
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step computed (loss, MLM/NSP scores, gradients, "
+                        "parameters) as DIR/<name>.npy in float32; large "
+                        "arrays are a fixed seeded sample (see dump_outputs). "
+                        "grads.npy is empty when --steps is a multiple of "
+                        "--accumulation: the last step then ends with the "
+                        "optimizer update, which clears the gradients")
+    p.add_argument("--full", action="store_true",
+                   help="also run the measurements and checks that the "
+                        "headline figure does not need. A plain run only "
+                        "sets up, warms up, times --steps steps and prints "
+                        "the result line; anything beyond that belongs "
+                        "behind this flag (there is none at present)")
     return p.parse_args()
+
+
+# --dump-outputs budget: 64 MB in all, float32. Gradients and parameters
+# get at most DUMP_GROUP_ELEMS elements each (2 x 24 MB); the rest is small.
+DUMP_GROUP_ELEMS = 6 * 1024 * 1024
+DUMP_SAMPLE_SEED = 20240229
+
+
+def _sample_flat(t, n, gen):
+    """`t` flattened to float32 on the CPU; if it has more than `n`
+    elements, a seeded sample of `n` of them (indices drawn from `gen`,
+    a CPU generator, so they depend only on the seed and the shapes)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        idx = torch.randint(0, flat.numel(), (n,), generator=gen)
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu()
+
+
+def dump_outputs(out_dir, last, named_params):
+    """Write what the last timed step handed back as <out_dir>/<name>.npy.
+
+    loss          the step's (accumulation-scaled) loss, shape (1,)
+    mlm_loss      the model's first return value: the scalar masked-LM
+                  loss of the fused decoder+CE path, shape (1,)
+    nsp_scores    next-sentence logits, whole (absent without NSP head)
+    mlm_labels    gathered masked-LM labels, whole
+    grads        gradients left in .grad after the step (empty when the
+                  step ended with the optimizer update, which clears them)
+    params        parameters after the step
+    grads/params concatenate, in named_parameters() order, a seeded sample
+    of each tensor sized in proportion to its share of all elements.
+    """
+    import numpy as np  # noqa: PLC0415
+
+    os.makedirs(out_dir, exist_ok=True)
+    gen = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+    loss, mlm_loss, rel, glabels = last
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu(),
+        "mlm_loss": mlm_loss.detach().float().reshape(1).cpu(),
+        "mlm_labels": glabels.detach().reshape(-1).float().cpu(),
+    }
+    if rel is not None:
+        arrays["nsp_scores"] = rel.detach().float().cpu()
+    total = sum(p.numel() for _, p in named_params)
+    frac = min(1.0, DUMP_GROUP_ELEMS / max(1, total))
+    g_parts, p_parts = [], []
+    for _, prm in named_params:
+        n = max(1, int(prm.numel() * frac))
+        p_parts.append(_sample_flat(prm, n, gen))
+        if prm.grad is not None:
+            g_parts.append(_sample_flat(prm.grad, n, gen))
+    arrays["params"] = torch.cat(p_parts)
+    arrays["grads"] = torch.cat(g_parts) if g_parts else torch.zeros(0)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                arr.numpy().astype(np.float32, copy=False))
 
 
 def make_batch(gen, device, bsz, seq, vocab, max_pred):
@@ -219,7 +298,7 @@ def main():
     wa = WindowAutocast()
     per_step_ac = ac_enabled and not args.window_autocast
 
-    def one_step(micro_idx: int) -> None:
+    def one_step(micro_idx: int):
         batch = make_batch(gen, device, bsz, seq, vocab_unpadded, phase["max_pred"])
         ids, tt, mask, labels, nsp = batch
         sync = (micro_idx + 1) % accum == 0
@@ -244,6 +323,9 @@ def main():
                 preconditioner.step()
             optimizer.step()
             optimizer.zero_grad(set_to_none=True)
+        # what a caller of the step receives (kept for --dump-outputs)
+        return (loss.detach(), scores.detach(),
+                None if rel is None else rel.detach(), glabels)
 
     model.train()
     for i in range(args.warmup):
@@ -254,8 +336,9 @@ def main():
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        one_step(i)
+        last = one_step(i)
     if use_cuda:
         torch.cuda.synchronize()
     wa.close()
@@ -268,6 +351,9 @@ def main():
         t = t.to(device) if use_cuda else t
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
     elapsed_max = float(t[0])
+
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, last, named)
 
     value = world * bsz * args.steps / elapsed_max
     if rank == 0:

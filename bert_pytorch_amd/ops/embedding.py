@@ -2,8 +2,9 @@
 
 One kernel for ``BertEmbeddings``'s word+position(+token-type) gather,
 sum, LayerNorm and dropout (reference: src/modeling.py:338-373).
-Backward scatter-adds into a dense fp32 word-embedding gradient with
-device-scope atomics. Kernel source: csrc/ops/embedding.hip.
+Backward scatter-adds into a dense fp32 word-embedding gradient in a
+fixed order (ids sorted, runs of one id summed in sequence; no float
+atomics). Kernel source: csrc/ops/embedding.hip.
 """
 
 from __future__ import annotations

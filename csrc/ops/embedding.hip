@@ -4,10 +4,11 @@
 //   z = word[ids] + pos[s] (+ tok[tt]) ; y = dropout(LN(z))
 // Tables may be fp32 (autocast mode) or bf16/fp16 (pure-bf16 master-
 // weight mode); the output is emitted in the requested dtype. Backward:
-// dz from LN-backward (stored to a fp32 buffer), then deterministic
-// pos/token-type reductions and an atomic scatter-add into a dense fp32
+// dz from LN-backward (stored to a fp32 buffer), then pos/token-type
+// reductions and a sorted, fixed-order scatter-add into a dense fp32
 // word-embedding gradient (cast to the table dtype by the Python
-// wrapper when the tables are low-precision).
+// wrapper when the tables are low-precision). No float atomics: every
+// gradient is bitwise identical from run to run.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -190,17 +191,91 @@ __global__ void embed_bwd_dz_kernel(
   }
 }
 
-// backward stage 2a: word-embedding scatter-add (atomic; duplicate ids rare)
-__global__ void embed_bwd_word_kernel(const float* __restrict__ dz,
-                                      const int64_t* __restrict__ ids,
-                                      float* __restrict__ d_word, int64_t rows,
-                                      int H) {
-  const int64_t total = rows * H;
-  for (int64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int64_t r = i / H;
-    const int c = static_cast<int>(i % H);
-    atomicAdd(&d_word[ids[r] * H + c], dz[i]);
+// backward stage 2a: word-embedding scatter-add in a fixed order, so that
+// rows of a repeated id ([MASK], [CLS], ...) sum bitwise identically from
+// run to run (float atomics add in arrival order and do not). The ids
+// come stably sorted (`sorted`, with `perm` the source row of each
+// position). Block b walks positions [b*kWordRows, (b+1)*kWordRows): a run
+// of one id that lies strictly inside is stored to d_word directly; the
+// piece that begins at the block's first position goes to head[b], the
+// piece that reaches its last position to tail[b] (head[b] if the whole
+// block is one run). embed_bwd_word_join_kernel then folds the pieces of
+// each run that touches a block edge, in block order. One writer per id.
+constexpr int kWordRows = 16;
+
+__global__ void embed_bwd_word_runs_kernel(const float* __restrict__ dz,
+                                           const int64_t* __restrict__ sorted,
+                                           const int64_t* __restrict__ perm,
+                                           float* __restrict__ d_word,
+                                           float* __restrict__ head,
+                                           float* __restrict__ tail, int rows,
+                                           int H) {
+  const int p0 = blockIdx.x * kWordRows;
+  const int p1 = min(p0 + kWordRows, rows);
+  const int64_t boff = static_cast<int64_t>(blockIdx.x) * H;
+  for (int c = threadIdx.x; c < H; c += blockDim.x) {
+    float acc = 0.f;
+    int run_start = p0;
+    for (int i = p0; i < p1; ++i) {
+      const int64_t id = sorted[i];
+      acc += dz[perm[i] * H + c];
+      const bool to_end = i + 1 == p1;
+      if (to_end || sorted[i + 1] != id) {
+        if (run_start == p0) head[boff + c] = acc;
+        else if (to_end) tail[boff + c] = acc;
+        else d_word[id * H + c] = acc;
+        acc = 0.f;
+        run_start = i + 1;
+      }
+    }
+  }
+}
+
+__global__ void embed_bwd_word_join_kernel(const int64_t* __restrict__ sorted,
+                                           const float* __restrict__ head,
+                                           const float* __restrict__ tail,
+                                           float* __restrict__ d_word,
+                                           int rows, int H, int nblocks) {
+  const int b = blockIdx.x;
+  const int p0 = b * kWordRows;
+  const int p1 = min(p0 + kWordRows, rows);
+  const int64_t first = sorted[p0];
+  const int64_t last = sorted[p1 - 1];
+  for (int cand = 0; cand < 2; ++cand) {
+    int64_t id;
+    const float* piece;
+    if (cand == 0) {
+      // the run that begins exactly at this block's first position
+      if (b > 0 && sorted[p0 - 1] == first) continue;
+      id = first;
+      piece = head + static_cast<int64_t>(b) * H;
+    } else {
+      // the run that begins inside this block and reaches its end
+      if (last == first) continue;
+      id = last;
+      piece = tail + static_cast<int64_t>(b) * H;
+    }
+    // The run reaches this block's end, so it may go on: its last
+    // position is upper_bound(id) - 1 (binary search; the fold below then
+    // has no data-dependent branch and its loads pipeline). Every block
+    // up to the one holding that position begins with `id`, i.e. its
+    // head piece belongs to this run.
+    int bb_end = b;
+    if (last == id) {
+      int lo = p1, hi = rows;  // first position in [p1, rows] with sorted != id
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted[mid] == id) lo = mid + 1;
+        else hi = mid;
+      }
+      bb_end = (lo - 1) / kWordRows;
+    }
+    for (int c = threadIdx.x; c < H; c += blockDim.x) {
+      float acc = piece[c];
+      for (int bb = b + 1; bb <= bb_end; ++bb)
+        acc += head[static_cast<int64_t>(bb) * H + c];
+      d_word[id * H + c] = acc;
+    }
   }
 }
 
@@ -226,19 +301,19 @@ __global__ void embed_bwd_tok_kernel(const float* __restrict__ dz,
                                      const int64_t* __restrict__ tt,
                                      float* __restrict__ parts, int rows, int H,
                                      int n_types, int rows_per_block) {
-  const int lane = threadIdx.x & (WAVE_SIZE - 1);
-  const int wave = threadIdx.x / WAVE_SIZE;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* lt = reinterpret_cast<float*>(smem_raw);  // [n_types][H]
   for (int c = threadIdx.x; c < n_types * H; c += blockDim.x) lt[c] = 0.f;
   __syncthreads();
   const int row0 = blockIdx.x * rows_per_block;
   const int row_end = min(row0 + rows_per_block, rows);
-  for (int r = row0 + wave; r < row_end; r += NW) {
-    const int t = static_cast<int>(tt[r]);
-    const int64_t base = static_cast<int64_t>(r) * H;
-    for (int c = lane; c < H; c += WAVE_SIZE)
-      atomicAdd(&lt[t * H + c], dz[base + c]);
+  // each thread owns its columns and walks the rows in order: no two
+  // threads touch one LDS cell, so the sum order is fixed (no atomics)
+  for (int c = threadIdx.x; c < H; c += blockDim.x) {
+    for (int r = row0; r < row_end; ++r) {
+      const int t = static_cast<int>(tt[r]);
+      lt[t * H + c] += dz[static_cast<int64_t>(r) * H + c];
+    }
   }
   __syncthreads();
   float* out = parts + static_cast<int64_t>(blockIdx.x) * n_types * H;
@@ -381,17 +456,33 @@ std::vector<torch::Tensor> embedding_ln_dropout_bwd(
   });
 
   auto d_word = torch::zeros({vocab, H}, fopts);
-  auto d_pos = torch::empty({max_pos, H}, fopts);
+  // zeros: embed_bwd_pos_kernel writes rows [0, seq_len) only, and the
+  // positions past seq_len must get a zero gradient, not leftover memory
+  auto d_pos = seq_len < max_pos ? torch::zeros({max_pos, H}, fopts)
+                                 : torch::empty({max_pos, H}, fopts);
   auto d_tok = has_tok ? torch::empty({n_types, H}, fopts)
                        : torch::empty({0}, fopts);
   auto dgamma = col_reduce_full(part_g);
   auto dbeta = col_reduce_full(part_b);
 
-  const int64_t total = static_cast<int64_t>(rows) * H;
-  const int sblocks = static_cast<int>(std::min<int64_t>((total + 255) / 256, 2048));
-  hipLaunchKernelGGL(embed_bwd_word_kernel, dim3(sblocks), dim3(256), 0,
-                     stream, dz.data_ptr<float>(), ids_c.data_ptr<int64_t>(),
-                     d_word.data_ptr<float>(), rows, H);
+  if (rows > 0) {
+    auto sorted_perm = ids_c.view({-1}).sort(/*stable=*/true, /*dim=*/0,
+                                            /*descending=*/false);
+    auto sorted = std::get<0>(sorted_perm).contiguous();
+    auto perm = std::get<1>(sorted_perm).contiguous();
+    const int wblocks = (rows + kWordRows - 1) / kWordRows;
+    auto head = torch::empty({wblocks, H}, fopts);
+    auto tail = torch::empty({wblocks, H}, fopts);
+    hipLaunchKernelGGL(embed_bwd_word_runs_kernel, dim3(wblocks), dim3(256), 0,
+                       stream, dz.data_ptr<float>(),
+                       sorted.data_ptr<int64_t>(), perm.data_ptr<int64_t>(),
+                       d_word.data_ptr<float>(), head.data_ptr<float>(),
+                       tail.data_ptr<float>(), rows, H);
+    hipLaunchKernelGGL(embed_bwd_word_join_kernel, dim3(wblocks), dim3(256), 0,
+                       stream, sorted.data_ptr<int64_t>(),
+                       head.data_ptr<float>(), tail.data_ptr<float>(),
+                       d_word.data_ptr<float>(), rows, H, wblocks);
+  }
   const int64_t ptotal = static_cast<int64_t>(seq_len) * H;
   const int pblocks = static_cast<int>(std::min<int64_t>((ptotal + 255) / 256, 2048));
   hipLaunchKernelGGL(embed_bwd_pos_kernel, dim3(pblocks), dim3(256), 0,

@@ -235,31 +235,77 @@ __global__ void col_reduce_blocked_kernel(const float* __restrict__ parts,
   for (int k = 0; k < 4 && c + k < S; ++k) dst[k] = acc[k];
 }
 
-// atomic accumulate variant: one launch, chunked rows per y-block.
-// Measured fastest at the [0.7k-1.5k rows, 2-12k cols] partial shapes
-// (the deterministic two-pass variants lose to it on second-pass
-// parallelism); fp32 atomics over a zeroed output, still bitwise
-// reproducible per launch geometry.
-__global__ void col_reduce_atomic_kernel(const float* __restrict__ parts,
-                                         int nparts, int S,
-                                         float* __restrict__ out) {
+// One-launch variant for many partial rows: `chunk` rows per y-block,
+// each y-block stores its chunk sum to tmp[y][S]; the y-block that
+// arrives last at its column strip (integer ticket in counters[x]) folds
+// tmp in y order. Same parallelism as accumulating with float atomics
+// (fastest at the [0.7k-1.5k rows, 2-12k cols] partial shapes), but the
+// summation order is fixed, so the result is bitwise identical from run
+// to run; float atomics land in arrival order and are not.
+__global__ void col_reduce_ordered_kernel(const float* __restrict__ parts,
+                                          int nparts, int S, int chunk,
+                                          float* __restrict__ tmp,
+                                          unsigned int* __restrict__ counters,
+                                          float* __restrict__ out) {
   const int c = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (c >= S) return;
-  const int p0 = blockIdx.y * kColChunk;
-  const int p1 = min(p0 + kColChunk, nparts);
-  float acc[4] = {};
-  for (int p = p0; p < p1; ++p) {
-    const float* src = parts + static_cast<int64_t>(p) * S + c;
-    if (c + 4 <= S) {
-      float v[4];
-      *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(src);
+  const bool active = c < S;
+  if (active) {
+    const int p0 = blockIdx.y * chunk;
+    const int p1 = min(p0 + chunk, nparts);
+    float acc[4] = {};
+    for (int p = p0; p < p1; ++p) {
+      const float* src = parts + static_cast<int64_t>(p) * S + c;
+      if (c + 4 <= S) {
+        float v[4];
+        *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(src);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) acc[k] += v[k];
-    } else {
-      for (int k = 0; c + k < S; ++k) acc[k] += src[k];
+        for (int k = 0; k < 4; ++k) acc[k] += v[k];
+      } else {
+        for (int k = 0; c + k < S; ++k) acc[k] += src[k];
+      }
     }
+    float* dst = tmp + static_cast<int64_t>(blockIdx.y) * S + c;
+    for (int k = 0; k < 4 && c + k < S; ++k) dst[k] = acc[k];
   }
-  for (int k = 0; k < 4 && c + k < S; ++k) atomicAdd(&out[c + k], acc[k]);
+  __threadfence();  // chunk sums visible device-wide before the ticket
+  __shared__ bool is_last;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    is_last = atomicAdd(&counters[blockIdx.x], 1u) == gridDim.y - 1;
+  __syncthreads();
+  if (!is_last || !active) return;
+  __threadfence();
+  // The writers fenced (agent scope) before taking their ticket, and the
+  // agent-scope fence above, after this block saw the last ticket,
+  // invalidates this CU's vector cache; so the plain wide loads below see
+  // every block's stores. kFoldBatch rows are loaded at a time so their
+  // latencies overlap; they are added in y order.
+  constexpr int kFoldBatch = 16;
+  const int ny = static_cast<int>(gridDim.y);
+  const int nk = min(4, S - c);
+  float sum[4] = {};
+  for (int j0 = 0; j0 < ny; j0 += kFoldBatch) {
+    float v[kFoldBatch][4];
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u) {
+      // rows past ny re-read the last row; their values are not added
+      const int j = min(j0 + u, ny - 1);
+      const float* src = tmp + static_cast<int64_t>(j) * S + c;
+      if (nk == 4) {
+        *reinterpret_cast<uint4*>(v[u]) =
+            *reinterpret_cast<const uint4*>(src);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[u][k] = k < nk ? src[k] : 0.f;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kFoldBatch; ++u)
+      if (j0 + u < ny) {
+        for (int k = 0; k < 4; ++k) sum[k] += v[u][k];
+      }
+  }
+  for (int k = 0; k < nk; ++k) out[c + k] = sum[k];
 }
 
 torch::Tensor col_reduce_full(torch::Tensor parts) {
@@ -274,10 +320,19 @@ torch::Tensor col_reduce_full(torch::Tensor parts) {
                        S, nparts, out.data_ptr<float>());
     return out;
   }
-  auto out = torch::zeros({S}, parts.options());
-  dim3 grid(xblocks, (nparts + kColChunk - 1) / kColChunk);
-  hipLaunchKernelGGL(col_reduce_atomic_kernel, grid, dim3(256), 0, stream,
-                     parts.data_ptr<float>(), nparts, S,
+  // 32 partial rows per y-block: measured best of 16/32/64/128 (fewer
+  // chunk sums shorten the last block's fold, longer chunks cost
+  // parallelism in the first phase)
+  const int chunk = 2 * kColChunk;
+  const int yblocks = (nparts + chunk - 1) / chunk;
+  auto out = torch::empty({S}, parts.options());
+  auto tmp = torch::empty({yblocks, S}, parts.options());
+  auto counters = torch::zeros({xblocks}, parts.options().dtype(torch::kInt32));
+  dim3 grid(xblocks, yblocks);
+  hipLaunchKernelGGL(col_reduce_ordered_kernel, grid, dim3(256), 0, stream,
+                     parts.data_ptr<float>(), nparts, S, chunk,
+                     tmp.data_ptr<float>(),
+                     reinterpret_cast<unsigned int*>(counters.data_ptr<int>()),
                      out.data_ptr<float>());
   return out;
 }

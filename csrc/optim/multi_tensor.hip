@@ -134,7 +134,29 @@ __global__ void l2norm_sq_kernel(const int64_t* __restrict__ ptrs,
   for (int i = threadIdx.x; i < n; i += blockDim.x) acc += g[i] * g[i];
   __shared__ float smem[kThreads / WAVE_SIZE];
   acc = block_reduce_sum<kThreads / WAVE_SIZE>(acc, smem);
-  if (threadIdx.x == 0) atomicAdd(out, acc);
+  if (threadIdx.x == 0) out[chunk] = acc;  // per-chunk partial
+}
+
+// Fold per-chunk partials in a fixed order (one block; thread i takes
+// chunks i, i+kThreads, ... then a fixed-shape block reduce), so the sum
+// is bitwise identical from run to run, which float atomics are not.
+// With `chunks` given, block t folds only tensor t's chunks and `stride`
+// interleaved values per chunk (LAMB: ||p||^2, ||u||^2).
+__global__ void fold_partials_kernel(const float* __restrict__ partials,
+                                     const int* __restrict__ chunks,
+                                     float* __restrict__ out, int n_chunks,
+                                     int stride) {
+  const int t = blockIdx.x;
+  __shared__ float smem[kThreads / WAVE_SIZE];
+  for (int k = 0; k < stride; ++k) {
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n_chunks; i += blockDim.x)
+      if (chunks == nullptr || chunks[i * 3] == t)
+        acc += partials[i * stride + k];
+    acc = block_reduce_sum<kThreads / WAVE_SIZE>(acc, smem);
+    if (threadIdx.x == 0) out[t * stride + k] = acc;
+    __syncthreads();
+  }
 }
 
 __global__ void clip_scale_kernel(const int64_t* __restrict__ ptrs,
@@ -155,7 +177,8 @@ __global__ void clip_scale_kernel(const int64_t* __restrict__ ptrs,
 }
 
 // LAMB stage 1: m/v update, bias-corrected Adam direction (+wd*p) written
-// over the grad buffer; per-tensor ||p||^2 and ||u||^2 into norms[t][2].
+// over the grad buffer; per-chunk ||p||^2 and ||u||^2 into norms[chunk][2]
+// (fold_partials_kernel then adds them per tensor in a fixed order).
 __global__ void lamb_stage1_kernel(
     const int64_t* __restrict__ ptrs,  // [4][n]: p, g, m, v
     const int64_t* __restrict__ sizes, const int* __restrict__ chunks,
@@ -193,9 +216,9 @@ __global__ void lamb_stage1_kernel(
   pn = block_reduce_sum<kThreads / WAVE_SIZE>(pn, smem);
   __syncthreads();
   un = block_reduce_sum<kThreads / WAVE_SIZE>(un, smem);
-  if (threadIdx.x == 0) {
-    atomicAdd(&norms[t * 2], pn);
-    atomicAdd(&norms[t * 2 + 1], un);
+  if (threadIdx.x == 0) {  // per-chunk partials, folded per tensor after
+    norms[chunk * 2] = pn;
+    norms[chunk * 2 + 1] = un;
   }
 }
 
@@ -254,12 +277,17 @@ torch::Tensor multi_tensor_l2norm_sq(std::vector<torch::Tensor> tensors) {
   TORCH_CHECK(!tensors.empty(), "l2norm: empty list");
   auto device = tensors[0].device();
   auto meta = build_chunks({tensors}, device);
-  auto out = torch::zeros({1}, tensors[0].options().dtype(torch::kFloat32));
+  auto fopts = tensors[0].options().dtype(torch::kFloat32);
+  auto partials = torch::empty({meta.n_chunks}, fopts);
+  auto out = torch::empty({1}, fopts);
   auto stream = at::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(l2norm_sq_kernel, dim3(meta.n_chunks), dim3(kThreads), 0,
                      stream, meta.ptrs.data_ptr<int64_t>(),
                      meta.sizes.data_ptr<int64_t>(), meta.chunks.data_ptr<int>(),
-                     out.data_ptr<float>(), meta.n_chunks);
+                     partials.data_ptr<float>(), meta.n_chunks);
+  hipLaunchKernelGGL(fold_partials_kernel, dim3(1), dim3(kThreads), 0, stream,
+                     partials.data_ptr<float>(), nullptr,
+                     out.data_ptr<float>(), meta.n_chunks, 1);
   return out.squeeze(0);
 }
 
@@ -286,7 +314,9 @@ void fused_lamb(std::vector<torch::Tensor> params,
   TORCH_CHECK(n > 0, "fused_lamb: empty");
   auto device = params[0].device();
   auto meta = build_chunks({params, grads, ms, vs}, device);
-  auto norms = torch::zeros({n, 2}, params[0].options().dtype(torch::kFloat32));
+  auto fopts = params[0].options().dtype(torch::kFloat32);
+  auto chunk_norms = torch::empty({meta.n_chunks, 2}, fopts);
+  auto norms = torch::empty({n, 2}, fopts);
   auto gsq = gnorm_sq.reshape({1}).contiguous();
   const float bc1 = bias_correction ? 1.f - powf(beta1, step) : 1.f;
   const float bc2 = bias_correction ? 1.f - powf(beta2, step) : 1.f;
@@ -295,11 +325,15 @@ void fused_lamb(std::vector<torch::Tensor> params,
   hipLaunchKernelGGL(lamb_stage1_kernel, dim3(meta.n_chunks), dim3(kThreads),
                      0, stream, meta.ptrs.data_ptr<int64_t>(),
                      meta.sizes.data_ptr<int64_t>(), meta.chunks.data_ptr<int>(),
-                     gsq.data_ptr<float>(), norms.data_ptr<float>(), n,
+                     gsq.data_ptr<float>(), chunk_norms.data_ptr<float>(), n,
                      meta.n_chunks, static_cast<float>(beta1),
                      static_cast<float>(beta2), static_cast<float>(eps),
                      static_cast<float>(wd), bc1, bc2, beta1_g,
                      static_cast<float>(max_grad_norm));
+  hipLaunchKernelGGL(fold_partials_kernel, dim3(n), dim3(kThreads), 0, stream,
+                     chunk_norms.data_ptr<float>(),
+                     meta.chunks.data_ptr<int>(), norms.data_ptr<float>(),
+                     meta.n_chunks, 2);
   hipLaunchKernelGGL(lamb_stage2_kernel, dim3(meta.n_chunks), dim3(kThreads),
                      0, stream, meta.ptrs.data_ptr<int64_t>(),
                      meta.sizes.data_ptr<int64_t>(), meta.chunks.data_ptr<int>(),

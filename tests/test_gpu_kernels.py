@@ -173,6 +173,176 @@ def test_embedding_fwd_bwd():
     assert rel_err(dlb, lb.grad) < 1e-3
 
 
+def _ids_from_counts(counts, rows, gen):
+    """Ids with the given multiplicities, shuffled over `rows` positions."""
+    flat = torch.cat([torch.full((n,), i, dtype=torch.long) for i, n in counts])
+    assert flat.numel() == rows
+    return flat[torch.randperm(rows, generator=gen)]
+
+
+def _embedding_id_cases():
+    # rows = 5 * 61 = 305 = 19 blocks of kWordRows (16) sorted positions + 1.
+    # After the kernel's stable sort the runs of "edges" lie as follows:
+    #   id 3   x16  positions   0-15   exactly block 0 (head, ends at edge)
+    #   id 7   x5   positions  16-20   from a block's start, ends inside
+    #   id 9   x1   position   21      interior single (direct store)
+    #   id 11  x75  positions  22-96   from mid block 1 over blocks 2-5
+    #                                  (whole-block pieces) into block 6
+    #   id 20  x15  positions  97-111  from inside block 6 to its edge
+    #   id 21  x32  positions 112-143  exactly blocks 7 and 8
+    #   ids 30-141  singles   144-255  block starts/ends as single runs
+    #   id 900 x49  positions 256-304  blocks 16-18 and the one-row last
+    #                                  block: reaches the last position
+    rows = 305
+    edges = [(3, 16), (7, 5), (9, 1), (11, 75), (20, 15), (21, 32)]
+    edges += [(30 + i, 1) for i in range(112)] + [(900, 49)]
+    # benchmark-like: 15 % one id ([MASK]), 1 per sequence another ([CLS])
+    masky = [(103, 46), (101, 5)] + [(200 + i, 1) for i in range(254)]
+    return {"edges": edges, "one_id": [(999, rows)], "mask_heavy": masky}
+
+
+@pytest.mark.parametrize("case", ["edges", "one_id", "mask_heavy"])
+def test_embedding_bwd_repeated_ids(case):
+    """Word-embedding gradient with runs of one id that cross the sorted
+    16-row blocks of the ordered scatter (whole-block runs, runs ending on
+    a block edge, a run reaching the last position), against the fp32
+    autograd composite, and bitwise equal between two launches.
+
+    Bound 1e-3 as in test_embedding_fwd_bwd: same reference, and the
+    longest sum here (305 fp32 terms, error <= 305 * 2^-24 of the sum of
+    magnitudes) stays far inside it."""
+    B, S, H, V, P, T = 5, 61, 1024, 1000, 64, 2
+    gen = torch.Generator().manual_seed(55)
+    ids = _ids_from_counts(_embedding_id_cases()[case], B * S, gen)
+    ids = ids.view(B, S).to(DEV)
+    torch.manual_seed(6)
+    tt = torch.randint(0, T, (B, S), device=DEV)
+    word = torch.randn(V, H, device=DEV, requires_grad=True)
+    pos = torch.randn(P, H, device=DEV, requires_grad=True)
+    tok = torch.randn(T, H, device=DEV, requires_grad=True)
+    w = (torch.randn(H, device=DEV) * 0.1 + 1.0).requires_grad_(True)
+    lb = (torch.randn(H, device=DEV) * 0.1).requires_grad_(True)
+    y_ref = ref.embedding_ln_dropout(ids, tt, word, pos, tok, w, lb, 0.0, False)
+    dy = torch.randn_like(y_ref)
+    y_ref.backward(dy)
+
+    y, z, mask, mean, rstd = ext().embedding_ln_dropout_fwd(
+        ids, tt, word.detach(), pos.detach(), tok.detach(), w.detach(),
+        lb.detach(), 0.0, 1e-12, 0, 0, torch.float32,
+    )
+    outs = [
+        ext().embedding_ln_dropout_bwd(
+            dy, ids, tt, z, mask, w.detach(), mean, rstd, 0.0, V, P, T
+        )
+        for _ in range(2)
+    ]
+    d_word, d_pos, d_tok, dw, dlb = outs[0]
+    assert rel_err(d_word, word.grad) < 1e-3
+    # rows of ids that do not occur stay exactly zero
+    absent = torch.ones(V, dtype=torch.bool, device=DEV)
+    absent[ids.view(-1)] = False
+    assert float(d_word[absent].abs().max()) == 0.0
+    assert rel_err(d_tok, tok.grad) < 1e-3
+    assert rel_err(d_pos, pos.grad) < 1e-3
+    assert rel_err(dw, w.grad) < 1e-3
+    assert rel_err(dlb, lb.grad) < 1e-3
+    for a, b in zip(*outs):
+        assert torch.equal(a, b), "two launches differ bitwise"
+
+
+# ---------------------------------------------------------------------------
+# ordered column reduce (many partial rows) and ordered norm reductions
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize(
+    "rows,H",
+    [
+        (1573, 1028),  # 50 partials: 2 chunks of 32, last short; 2nd strip 4 cols
+        (4160, 2048),  # 130 partials: 5 chunks, two full strips
+        (16500, 1028),  # 516 partials: 17 chunks, more than one fold batch (16)
+    ],
+)
+def test_col_sum_ordered_reduce(rows, H):
+    """col_sum through the one-launch ordered column reduce (more than 48
+    partial rows): every column within the fp32 summation bound
+    rows * 2^-24 * sum|x| of the fp64 sum, and bitwise equal between two
+    launches."""
+    torch.manual_seed(20)
+    x = torch.randn(rows, H, device=DEV)
+    a = ext().col_sum(x)
+    b = ext().col_sum(x)
+    ref64 = x.double().sum(0)
+    bound = rows * 2.0 ** -24 * x.double().abs().sum(0)
+    assert a.shape == (H,)
+    assert bool(((a.double() - ref64).abs() <= bound).all())
+    assert torch.equal(a, b), "two launches differ bitwise"
+
+
+def test_ln_backward_many_rows_repeatable():
+    """LayerNorm backward at a row count whose dgamma/dbeta partials take
+    the ordered column reduce (2000 rows -> 125 partial rows)."""
+    torch.manual_seed(21)
+    rows, H = 2000, 1024
+    x = torch.randn(rows, H, device=DEV)
+    w = (torch.randn(H, device=DEV) * 0.1 + 1.0).requires_grad_(True)
+    b = (torch.randn(H, device=DEV) * 0.1).requires_grad_(True)
+    xr = x.detach().clone().requires_grad_(True)
+    y_ref = ref.layer_norm(xr, w, b, 1e-12)
+    dy = torch.randn_like(y_ref)
+    y_ref.backward(dy)
+    _, mean, rstd = ext().ln_fwd(x, w.detach(), b.detach(), 1e-12)
+    o1 = ext().ln_bwd(dy, x, w.detach(), mean, rstd)
+    o2 = ext().ln_bwd(dy, x, w.detach(), mean, rstd)
+    # kernel and reference both sum `rows` fp32 terms per column, each
+    # within rows * 2^-24 * sum|term| of the exact sum; the normalised x
+    # in dgamma's terms carries a few more ulps, hence 2^-22 in all
+    xhat = (x - x.mean(1, keepdim=True)) * torch.rsqrt(
+        x.var(1, unbiased=False, keepdim=True) + 1e-12)
+    bound_b = rows * 2.0 ** -22 * dy.abs().sum(0)
+    bound_g = rows * 2.0 ** -22 * (dy * xhat).abs().sum(0)
+    assert bool(((o1[2] - b.grad).abs() <= bound_b).all())
+    assert bool(((o1[1] - w.grad).abs() <= bound_g).all())
+    for t1, t2 in zip(o1, o2):
+        assert torch.equal(t1, t2), "two launches differ bitwise"
+
+
+def test_l2norm_sq_ordered():
+    """Global grad-norm^2 over tensors of 4, 2, 1 and 1 chunks (64Ki
+    elements each): within n * 2^-24 of the fp64 value, bitwise equal
+    between two launches."""
+    torch.manual_seed(22)
+    ts = [torch.randn(n, device=DEV) for n in (200_000, 70_000, 5, 65_536)]
+    a = ext().multi_tensor_l2norm_sq(ts)
+    b = ext().multi_tensor_l2norm_sq(ts)
+    want = sum(float((t.double() ** 2).sum()) for t in ts)
+    n = sum(t.numel() for t in ts)
+    assert abs(float(a) - want) <= n * 2.0 ** -24 * want
+    assert torch.equal(a, b), "two launches differ bitwise"
+
+
+def test_fused_lamb_repeatable():
+    """Two FusedLAMB runs from equal states end bitwise equal; the
+    (30528, 8) tensor spans 4 chunks, so its trust-ratio norms are folded
+    from several per-chunk partials."""
+    from bert_pytorch_amd.optim import FusedLAMB
+
+    shapes = [(128, 128), (1024,), (30528, 8), (7,)]
+    torch.manual_seed(23)
+    init = [torch.randn(s, device=DEV) for s in shapes]
+    grads = [torch.randn(s, device=DEV) for s in shapes]
+    results = []
+    for _ in range(2):
+        params = [p.clone().requires_grad_(True) for p in init]
+        opt = FusedLAMB(params, lr=1e-2, weight_decay=0.01)
+        for step in range(3):
+            for p, g in zip(params, grads):
+                p.grad = (g * (step + 1)).clone()
+            opt.step()
+        results.append([p.detach().clone() for p in params])
+    for p1, p2, p0 in zip(results[0], results[1], init):
+        assert not torch.equal(p1, p0)
+        assert torch.equal(p1, p2), "two runs differ bitwise"
+
+
 # ---------------------------------------------------------------------------
 # cross entropy
 # ---------------------------------------------------------------------------
@@ -396,6 +566,58 @@ def test_model_step_bf16():
         losses.append(float(loss))
     assert all(l == l for l in losses), f"NaN loss: {losses}"
     assert losses[-1] < losses[0], f"loss did not drop: {losses}"
+
+
+def test_train_steps_bitwise_repeatable():
+    """Two trainings from one seed (dropout on, 1024 rows so that the
+    bias/LayerNorm gradients take the ordered column reduce, repeated
+    ids, three LAMB updates) end with bitwise equal losses and
+    parameters."""
+    from bert_pytorch_amd.config import BertConfig
+    from bert_pytorch_amd.models import (
+        BertForPreTraining,
+        BertPretrainingCriterion,
+    )
+    from bert_pytorch_amd.ops import rng
+    from bert_pytorch_amd.optim import FusedLAMB
+
+    def run():
+        torch.manual_seed(31)
+        rng.reset(31)
+        config = BertConfig(
+            vocab_size_or_config_json_file=2048, hidden_size=256,
+            num_hidden_layers=2, num_attention_heads=4,
+            intermediate_size=512, max_position_embeddings=128,
+        )
+        model = BertForPreTraining(config).to(DEV)
+        criterion = BertPretrainingCriterion(config.vocab_size)
+        opt = FusedLAMB(model.parameters(), lr=1e-3)
+        ids = torch.randint(0, 2048, (8, 128), device=DEV)
+        ids[:, 20:40] = 103  # a long run of one id for the sorted scatter
+        tt = torch.zeros_like(ids)
+        tt[:, 64:] = 1
+        mask = torch.ones_like(ids)
+        labels = torch.full_like(ids, -1)
+        labels[:, 20:40] = torch.randint(0, 2048, (8, 20), device=DEV)
+        nsp = torch.randint(0, 2, (8,), device=DEV)
+        losses = []
+        for _ in range(3):
+            opt.zero_grad()
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                scores, rel, gl = model(ids, tt, mask, masked_lm_labels=labels)
+                loss = criterion(scores, rel, gl, nsp)
+            loss.backward()
+            opt.step()
+            losses.append(loss.detach().clone())
+        return losses, [p.detach().clone() for p in model.parameters()]
+
+    l1, p1 = run()
+    l2, p2 = run()
+    assert all(bool(torch.isfinite(l)) for l in l1)
+    for a, b in zip(l1, l2):
+        assert torch.equal(a, b), "losses differ between two runs"
+    for a, b in zip(p1, p2):
+        assert torch.equal(a, b), "parameters differ between two runs"
 
 
 def test_gpu_matches_cpu_forward():
