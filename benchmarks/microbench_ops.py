@@ -5,7 +5,15 @@ against the measured copy ceiling (~6.3 TB/s) and against the eager
 PyTorch composition.
 
 Run (GPU box): python benchmarks/microbench_ops.py [--phase 1]
+                  [--dtype bf16|fp16]
 Prints one JSON line per op.
+
+``--section mfma`` times only the three MFMA kernels that exist in a
+bf16 and an fp16 instantiation (attention, split-K wgrad at the four
+encoder shapes next to the library's ``dy.t() @ x``, MLM head). With
+several ``--dtype`` values and ``--repeats N`` the dtypes alternate
+inside each repeat, so fp16 is compared with the bf16 run-to-run spread
+of the same process; a final summary line per op gives min/median/max.
 """
 
 from __future__ import annotations
@@ -56,17 +64,120 @@ def report(name, us, bytes_moved, extra=None):
     return rec
 
 
+DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
+
+
+def bench_mfma(phase, dtypes, repeats):
+    """attention / wgrad / MLM-head kernels, called through the
+    extension so nothing but the kernels under test is timed."""
+    dev = torch.device("cuda:0")
+    ext = ops.extension()
+    b, s = (96, 128) if phase == 1 else (16, 512)
+    rows = b * s
+    H, FFN, NH, V, P = 1024, 4096, 16, 30528, 1280
+    samples = {}
+
+    def timeit_long(fn):  # ~10-60 ms timed window per sample
+        return timeit(fn, iters=200, warmup=20)
+
+    def rec(name, dname, us, extra=None):
+        report(f"{name}[{dname}]", us, 0, extra)
+        samples.setdefault((name, dname), []).append(us)
+
+    inputs = {}
+    for dname in dtypes:
+        dt = DTYPES[dname]
+        torch.manual_seed(0)
+        inp = {
+            "qkv": (torch.randn(b, s, 3 * H, device=dev) * 0.5).to(dt),
+            "do": (torch.randn(b, s, H, device=dev) * 0.5).to(dt),
+            "h": (torch.randn(P, H, device=dev) * 0.5).to(dt),
+            "wv": (torch.randn(V, H, device=dev) * 0.05).to(dt),
+        }
+        # the four encoder wgrad shapes (M = out features, N = in)
+        for tag, (m, n) in {
+            "qkv": (3 * H, H), "attn_out": (H, H),
+            "ffn1": (FFN, H), "ffn2": (H, FFN),
+        }.items():
+            inp["dy_" + tag] = torch.randn(rows, m, device=dev, dtype=dt)
+            inp["x_" + tag] = torch.randn(rows, n, device=dev, dtype=dt)
+        inputs[dname] = inp
+    seqlens = torch.full((b,), s, device=dev, dtype=torch.int32)
+    bias_v = torch.randn(V, device=dev) * 0.1
+    labels = torch.randint(0, V, (P,), device=dev)
+    aflops = 4 * b * NH * s * s * 64
+
+    for _ in range(repeats):
+        for dname in dtypes:
+            inp = inputs[dname]
+            qkv, do = inp["qkv"], inp["do"]
+            for p_drop, sfx in ((0.0, ""), (0.1, "_drop")):
+                us = timeit_long(
+                    lambda: ext.attention_fwd(qkv, seqlens, NH, p_drop, 7, 0)
+                )
+                rec("attn_fwd" + sfx, dname, us,
+                    {"TFLOP_s": round(aflops / (us * 1e-6) / 1e12, 1)})
+                out, lse, dmask = ext.attention_fwd(
+                    qkv, seqlens, NH, p_drop, 7, 0
+                )
+                # delta + dK/dV kernel + dQ kernel (split per kernel:
+                # rocprofv3 --kernel-trace --stats on this same command)
+                us = timeit_long(
+                    lambda: ext.attention_bwd(
+                        do, qkv, seqlens, out, lse, dmask, NH, p_drop, 7, 0
+                    )
+                )
+                rec("attn_bwd" + sfx, dname, us,
+                    {"TFLOP_s": round(2.5 * aflops / (us * 1e-6) / 1e12, 1)})
+            for tag in ("qkv", "attn_out", "ffn1", "ffn2"):
+                dy, x = inp["dy_" + tag], inp["x_" + tag]
+                wflops = 2 * rows * dy.shape[1] * x.shape[1]
+                shape = f"K{rows}_M{dy.shape[1]}_N{x.shape[1]}"
+                us = timeit_long(lambda: ext.wgrad_tn(dy, x))
+                rec(f"wgrad_tn_{tag}_{shape}", dname, us,
+                    {"TFLOP_s": round(wflops / (us * 1e-6) / 1e12, 1),
+                     "routed_in_repo": bool(ext.wgrad_tn_profitable(
+                         rows, dy.shape[1], x.shape[1]))})
+                us = timeit_long(lambda: dy.t() @ x)
+                rec(f"wgrad_lib_{tag}_{shape}", dname, us,
+                    {"TFLOP_s": round(wflops / (us * 1e-6) / 1e12, 1)})
+            us = timeit_long(
+                lambda: ext.mlm_head_fwd(
+                    inp["h"], inp["wv"], bias_v, labels, -1
+                )
+            )
+            rec(f"mlm_head_fwd_P{P}", dname, us,
+                {"TFLOP_s": round(2 * P * H * V / (us * 1e-6) / 1e12, 1)})
+
+    for (name, dname), v in samples.items():
+        v = sorted(v)
+        print(json.dumps({
+            "summary": name, "dtype": dname, "n": len(v),
+            "min_us": round(v[0], 2), "median_us": round(v[len(v) // 2], 2),
+            "max_us": round(v[-1], 2),
+        }), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--phase", type=int, default=1, choices=[1, 2])
+    p.add_argument("--dtype", nargs="+", default=["bf16"],
+                   choices=sorted(DTYPES),
+                   help="16-bit element type(s); --section all uses the first")
+    p.add_argument("--section", default="all", choices=["all", "mfma"])
+    p.add_argument("--repeats", type=int, default=1,
+                   help="--section mfma: timed repeats per op and dtype")
     args = p.parse_args()
     assert torch.cuda.is_available()
+    if args.section == "mfma":
+        bench_mfma(args.phase, args.dtype, args.repeats)
+        return
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     b, s = (96, 128) if args.phase == 1 else (16, 512)
     rows = b * s
     H, FFN, NH, V = 1024, 4096, 16, 30528
-    dt = torch.bfloat16
+    dt = DTYPES[args.dtype[0]]
     e = 2  # bytes/elem
 
     # ---- ceiling: pure copy

@@ -1,7 +1,8 @@
 """Fused scaled-dot-product attention with padding mask (HIP, gfx950).
 
 Flash-style forward (online softmax over key tiles, MFMA
-``mfma_f32_16x16x32_bf16`` tiles, K/V staged through LDS) replacing the
+``mfma_f32_16x16x32_bf16`` / ``_f16`` tiles, K/V staged through LDS)
+for bf16 and fp16 inputs, replacing the
 reference's five-op attention path (QK^T, +mask, softmax, dropout, PV —
 src/modeling.py:403-429). Input is the packed QKV GEMM output
 ``[B, S, 3H]`` (no transpose kernels); the padding mask enters as per-
@@ -48,11 +49,12 @@ class _FusedAttention(torch.autograd.Function):
 
 def _kernel_supported(qkv: torch.Tensor, num_heads: int) -> bool:
     """The gfx950 MFMA kernel covers the BERT/RoBERTa operating points:
-    bf16, head_dim 64, S % 16 == 0. Other shapes (tiny test configs,
+    bf16 or fp16 (one kernel templated on the element type), head_dim
+    64, S % 16 == 0. Other shapes (tiny test configs,
     fp32-without-autocast) run the eager composite on device."""
     head_dim = qkv.shape[-1] // 3 // num_heads
     return (
-        qkv.dtype == torch.bfloat16
+        qkv.dtype in (torch.bfloat16, torch.float16)
         and head_dim == 64
         and qkv.shape[1] % 16 == 0
     )

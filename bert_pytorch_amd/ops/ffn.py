@@ -61,12 +61,14 @@ def ffn_supported(x: torch.Tensor) -> bool:
     global _aux_supported
     if not use_native(x):
         return False
-    # The epilogue GEMMs require bf16 inputs; outside autocast an fp32
-    # forward must take the standalone bias-GELU path instead (mirrors
-    # fused_attention's dtype gate).
-    if x.dtype != torch.bfloat16 and not (
-        x.is_cuda and torch.is_autocast_enabled()
-    ):
+    # The epilogue GEMMs require bf16 inputs. fused_ffn casts to the
+    # autocast dtype, so the EFFECTIVE dtype decides: fp16 (tensor or
+    # autocast) and fp32-outside-autocast take the standalone bias-GELU
+    # kernels instead, which support half and float.
+    eff = x.dtype
+    if x.is_cuda and torch.is_autocast_enabled():
+        eff = torch.get_autocast_dtype("cuda")
+    if eff != torch.bfloat16:
         return False
     if _aux_supported is None:
         _aux_supported = bool(extension().gemm_gelu_aux_supported())

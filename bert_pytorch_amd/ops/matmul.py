@@ -24,11 +24,18 @@ from . import extension, use_native
 
 
 def _wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
-    """dW = dy2^T @ x2 via the split-K kernel when supported."""
+    """dW = dy2^T @ x2 via the split-K kernel when supported.
+
+    bf16 or fp16, both operands alike. ``wgrad_tn_profitable``'s
+    thresholds were tuned against the bf16 library GEMMs and fp16 keeps
+    the same routing: a first fp16 measurement at the four encoder
+    shapes (profiles/fp16_kernels.md) shows the same winners as bf16,
+    but no fp16 sweep has been done, so nothing is retuned here.
+    """
     if (
         dy2.is_cuda
-        and dy2.dtype == torch.bfloat16
-        and x2.dtype == torch.bfloat16
+        and dy2.dtype in (torch.bfloat16, torch.float16)
+        and x2.dtype == dy2.dtype
         and extension().wgrad_tn_profitable(
             dy2.shape[0], dy2.shape[1], x2.shape[1]
         )

@@ -31,6 +31,11 @@ measured parity the in-repo MFMA kernel is the DEFAULT (the
 framework's biggest GEMM runs in-repo); BPA_FUSED_MLM=0 opts back
 into the library-GEMM path. Full parity coverage:
 tests/test_gpu_kernels.py::test_mlm_*.
+
+The kernel is instantiated for bf16 and fp16: the fused path runs in
+the hidden states' 16-bit dtype, or in the autocast GPU dtype when
+they are fp32, and the logits are materialized in that dtype (fp16:
+tests/test_gpu_fp16_kernels.py::test_mlm_*).
 """
 
 from __future__ import annotations
@@ -81,6 +86,22 @@ class _MlmDecoderLoss(torch.autograd.Function):
         return dh, dw, dbias, None, None
 
 
+_KERNEL_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def _kernel_dtype(hidden: torch.Tensor):
+    """16-bit dtype the fused kernel runs in: the hidden states' own
+    dtype if it is bf16/fp16, else the autocast GPU dtype if that is
+    bf16/fp16, else None (unfused path)."""
+    if hidden.dtype in _KERNEL_DTYPES:
+        return hidden.dtype
+    if torch.is_autocast_enabled():
+        dt = torch.get_autocast_gpu_dtype()
+        if dt in _KERNEL_DTYPES:
+            return dt
+    return None
+
+
 def mlm_decoder_loss(
     hidden: torch.Tensor,
     weight: torch.Tensor,
@@ -98,17 +119,14 @@ def mlm_decoder_loss(
         P, K = hidden.shape
         V = weight.shape[0]
         p_pad = ((P + _TILE - 1) // _TILE) * _TILE
-        bf16 = hidden.dtype == torch.bfloat16 or (
-            torch.is_autocast_enabled()
-            and torch.get_autocast_gpu_dtype() == torch.bfloat16
-        )
+        dtype = _kernel_dtype(hidden)
         if (
-            bf16
+            dtype is not None
             and ext.mlm_head_supported(p_pad, V, K)
             and os.environ.get("BPA_FUSED_MLM") != "0"  # opt-out (see above)
         ):
-            h = hidden.to(torch.bfloat16)
-            w = weight.to(torch.bfloat16)
+            h = hidden.to(dtype)
+            w = weight.to(dtype)
             b = bias.float()
             return _MlmDecoderLoss.apply(h, w, b, labels, ignore_index)
         # unfused native: library GEMM + fused CE kernel. Outside

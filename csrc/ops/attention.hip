@@ -2,7 +2,8 @@
 //
 // Replaces the reference's 5-op attention path (QK^T, +mask, softmax,
 // dropout, PV — src/modeling.py:403-429) with MFMA kernels built on
-// v_mfma_f32_16x16x32_bf16:
+// v_mfma_f32_16x16x32_bf16 / v_mfma_f32_16x16x32_f16 (one source,
+// templated on the 16-bit element type - csrc/mfma_types.h):
 //
 // Forward: grid (S/128 q-tiles, B*heads); 4 waves/block, 2x16 q-rows
 // per wave. K and V staged NATURALLY in LDS (K at a 72-elem stride for
@@ -45,16 +46,16 @@
 #include <utility>
 
 #include "../common.h"
+#include "../mfma_types.h"
 
 namespace bpa {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __hip_bfloat16 bf16_t;
+// Every MFMA kernel below is templated on the 16-bit element type T
+// (__bf16 or _Float16); Tr = Mfma16<T> supplies the fragment vector F8,
+// the MFMA, the transpose read and the fp32 conversions. Softmax, lse
+// and delta math is fp32 for both.
 
-#define MFMA16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16((A), (B), (C), 0, 0, 0)
-
-constexpr int kPad = 8;        // bf16 row pad: 72-element stride, bank-clean
+constexpr int kPad = 8;        // 16-bit row pad: 72-element stride, bank-clean
 constexpr int kStride = 64 + kPad;
 // Stride for LDS images read with ds_read_b64_tr_b16: 80 elements (40
 // dwords) makes the hardware transpose read conflict-free within its
@@ -65,21 +66,20 @@ constexpr int kStride = 64 + kPad;
 // gcd(stride_dw,64)=4, tr needs gcd=8).
 constexpr int kTrStride = 80;
 
-// Build an A/B fragment from a row-major bf16 row pointer: elements at
+// Build an A/B fragment from a row-major 16-bit row pointer: elements at
 // k = base + g*4 + (e&3) + 16*(e>>2), loaded as two 8-byte chunks.
-__device__ __forceinline__ bf16x8 frag_row(const __bf16* row, int base,
-                                           int g) {
+template <typename T>
+__device__ __forceinline__ typename Mfma16<T>::frag frag_row(const T* row,
+                                                             int base,
+                                                             int g) {
   union {
-    bf16x8 v;
+    typename Mfma16<T>::frag v;
     uint2 u[2];
   } r;
   r.u[0] = *reinterpret_cast<const uint2*>(row + base + g * 4);
   r.u[1] = *reinterpret_cast<const uint2*>(row + base + 16 + g * 4);
   return r.v;
 }
-
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4v;
-typedef __attribute__((address_space(3))) bf16x4v* lds_bf16x4p;
 
 // Transposed A/B fragment via gfx950's hardware transpose read, straight
 // from a NATURAL row-major [rows][kTrStride] bf16 LDS image: element
@@ -90,20 +90,20 @@ typedef __attribute__((address_space(3))) bf16x4v* lds_bf16x4p;
 // (g, t) points at 4 contiguous elements of row rb + g*4 + (t>>2) and
 // the instruction delivers the group-transposed fragment. Replaces the
 // per-thread 16x ds_write_b16 transpose scatter at staging time.
-__device__ __forceinline__ bf16x8 frag_tr(const __bf16* img, int rb,
-                                          int cb) {
+template <typename T>
+__device__ __forceinline__ typename Mfma16<T>::frag frag_tr(const T* img,
+                                                            int rb, int cb) {
+  using Tr = Mfma16<T>;
   const int lane = threadIdx.x & 63;
   const int g = (lane >> 4) & 3, t = lane & 15;
-  const __bf16* p0 =
+  const T* p0 =
       img + (rb + g * 4 + (t >> 2)) * kTrStride + cb + (t & 3) * 4;
   union {
-    bf16x8 v;
-    bf16x4v h[2];
+    typename Tr::frag v;
+    typename Tr::tr4 h[2];
   } r;
-  r.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4p)(p0));
-  r.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4p)(p0 + 16 * kTrStride));
+  r.h[0] = Tr::tr_read(p0);
+  r.h[1] = Tr::tr_read(p0 + 16 * kTrStride);
   return r.v;
 }
 
@@ -153,12 +153,14 @@ static inline std::pair<uint32_t, float> quantize_drop_p(double p) {
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-template <bool TRAIN_DROP>
+template <typename T, bool TRAIN_DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
-    const __bf16* __restrict__ qkv, const int* __restrict__ seqlens,
-    __bf16* __restrict__ out, float* __restrict__ lse_out,
+    const T* __restrict__ qkv, const int* __restrict__ seqlens,
+    T* __restrict__ out, float* __restrict__ lse_out,
     const uint32_t* __restrict__ dmask, int B, int S, int NH, float p,
     float scale, uint64_t seed, uint64_t offset) {
+  using Tr = Mfma16<T>;
+  using F8 = typename Tr::frag;
   // 4 waves x 32 q-rows (two 16-row subtiles per wave): the K/V tile is
   // staged once per 128 q-rows, each K/V fragment read feeds TWO
   // independent MFMA chains, and the softmax work of the two subtiles
@@ -171,9 +173,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   const int g = (lane >> 4), li = lane & 15;
   const int H = NH * 64;
   const int rs3 = 3 * H;  // qkv row stride
-  const __bf16* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
-  const __bf16* kbase = qbase + H;
-  const __bf16* vbase = qbase + 2 * H;
+  const T* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
+  const T* kbase = qbase + H;
+  const T* vbase = qbase + 2 * H;
   const int slen = seqlens[b];
   const float inv_keep = TRAIN_DROP ? 1.f / (1.f - p) : 1.f;
   const int Sw = (S + 31) >> 5;  // mask row stride in words
@@ -181,8 +183,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
       TRAIN_DROP ? dmask + static_cast<int64_t>(bh) * S * Sw : nullptr;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* K_lds = reinterpret_cast<__bf16*>(smem);             // [64][72]
-  __bf16* V_lds = K_lds + 64 * kStride;   // [64][80] natural, tr-read
+  T* K_lds = reinterpret_cast<T*>(smem);             // [64][72]
+  T* V_lds = K_lds + 64 * kStride;   // [64][80] natural, tr-read
   float* alpha_lds = reinterpret_cast<float*>(V_lds + 64 * kTrStride);  // [4][2][16]
   float* stat_lds = alpha_lds + 4 * 2 * 16;                    // [4][2][16]
   // keep-mask words for the current kv-tile, [128 q][2 words]: staged
@@ -192,7 +194,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 
   // this wave's two q-subtiles: rows q0 + wave*32 + sub*16 + li
   int q_row[2];
-  bf16x8 qfrag[2][2];
+  F8 qfrag[2][2];
 #pragma unroll
   for (int sub = 0; sub < 2; ++sub) {
     q_row[sub] = q0 + wave * 32 + sub * 16 + li;
@@ -246,14 +248,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const __bf16* krow = &K_lds[(t * 16 + li) * kStride];
-      const bf16x8 kf0 = frag_row(krow, 0, g);
-      const bf16x8 kf1 = frag_row(krow, 32, g);
+      const T* krow = &K_lds[(t * 16 + li) * kStride];
+      const F8 kf0 = frag_row(krow, 0, g);
+      const F8 kf1 = frag_row(krow, 32, g);
       f32x4 a0 = {}, a1 = {};
-      a0 = MFMA16(kf0, qfrag[0][0], a0);
-      a1 = MFMA16(kf0, qfrag[1][0], a1);
-      a0 = MFMA16(kf1, qfrag[0][1], a0);
-      a1 = MFMA16(kf1, qfrag[1][1], a1);
+      a0 = Tr::mfma(kf0, qfrag[0][0], a0);
+      a1 = Tr::mfma(kf0, qfrag[1][0], a1);
+      a0 = Tr::mfma(kf1, qfrag[0][1], a0);
+      a1 = Tr::mfma(kf1, qfrag[1][1], a1);
       s_acc[0][t] = a0;
       s_acc[1][t] = a1;
     }
@@ -323,30 +325,30 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     }
 
     // P fragments chain from sv; one V^T fragment feeds both subtiles
-    bf16x8 pa[2][2];
+    F8 pa[2][2];
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         union {
-          bf16x8 v;
-          __bf16 e[8];
+          F8 v;
+          T e[8];
         } pk;
 #pragma unroll
         for (int e = 0; e < 8; ++e)
-          pk.e[e] = __bf16(sv[sub][2 * c + (e >> 2)][e & 3]);
+          pk.e[e] = Tr::from_f32(sv[sub][2 * c + (e >> 2)][e & 3]);
         pa[sub][c] = pk.v;
       }
     }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-      const bf16x8 vf0 = frag_tr(V_lds, 0, n * 16);
-      const bf16x8 vf1 = frag_tr(V_lds, 32, n * 16);
-      acc_o[0][n] = MFMA16(pa[0][0], vf0, acc_o[0][n]);
-      acc_o[1][n] = MFMA16(pa[1][0], vf0, acc_o[1][n]);
-      acc_o[0][n] = MFMA16(pa[0][1], vf1, acc_o[0][n]);
-      acc_o[1][n] = MFMA16(pa[1][1], vf1, acc_o[1][n]);
+      const F8 vf0 = frag_tr(V_lds, 0, n * 16);
+      const F8 vf1 = frag_tr(V_lds, 32, n * 16);
+      acc_o[0][n] = Tr::mfma(pa[0][0], vf0, acc_o[0][n]);
+      acc_o[1][n] = Tr::mfma(pa[1][0], vf0, acc_o[1][n]);
+      acc_o[0][n] = Tr::mfma(pa[0][1], vf1, acc_o[0][n]);
+      acc_o[1][n] = Tr::mfma(pa[1][1], vf1, acc_o[1][n]);
     }
     __builtin_amdgcn_s_setprio(0);
   }
@@ -367,7 +369,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
           const float l = stat_lds[(wave * 2 + sub) * 16 + g * 4 + r];
           const float o = acc_o[sub][n][r] / (l > 0.f ? l : 1.f);
           out[(static_cast<int64_t>(b) * S + qr) * H + h * 64 + n * 16 + li] =
-              __bf16(o);
+              Tr::from_f32(o);
         }
       }
     }
@@ -386,8 +388,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 // touch 128 contiguous bytes), and the row sum needs only 3 xor-shuffle
 // rounds within the 8-lane group (the old wave-per-row version was
 // reduce-latency-bound at 0.17 TB/s).
-__global__ void attn_delta_kernel(const __bf16* __restrict__ dout,
-                                  const __bf16* __restrict__ out,
+template <typename T>
+__global__ void attn_delta_kernel(const T* __restrict__ dout,
+                                  const T* __restrict__ out,
                                   float* __restrict__ delta, int B, int S,
                                   int NH) {
   const int H = NH * 64;
@@ -404,13 +407,13 @@ __global__ void attn_delta_kernel(const __bf16* __restrict__ dout,
   const int b = static_cast<int>(bh) / NH, h = static_cast<int>(bh) % NH;
   const int64_t base =
       (static_cast<int64_t>(b) * S + q) * H + h * 64 + part * 8;
-  __bf16 dv[8], ov[8];
+  using Tr = Mfma16<T>;
+  T dv[8], ov[8];
   *reinterpret_cast<uint4*>(dv) = *reinterpret_cast<const uint4*>(dout + base);
   *reinterpret_cast<uint4*>(ov) = *reinterpret_cast<const uint4*>(out + base);
   float acc = 0.f;
 #pragma unroll
-  for (int k = 0; k < 8; ++k)
-    acc += __bfloat162float(dv[k]) * __bfloat162float(ov[k]);
+  for (int k = 0; k < 8; ++k) acc += Tr::to_f32(dv[k]) * Tr::to_f32(ov[k]);
 #pragma unroll
   for (int off = 4; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE_SIZE);
   if (part == 0) delta[row] = acc;
@@ -422,13 +425,15 @@ __global__ void attn_delta_kernel(const __bf16* __restrict__ dout,
 // lane registers into A-fragments for dQ += dS.K against K^T in LDS
 // (exactly how the forward chains P into the PV product). dQ stays in
 // registers until the single epilogue store into dqkv's Q slots.
-template <bool TRAIN_DROP>
+template <typename T, bool TRAIN_DROP>
 __global__ __launch_bounds__(256) void attn_dq_kernel(
-    const __bf16* __restrict__ dout, const __bf16* __restrict__ qkv,
+    const T* __restrict__ dout, const T* __restrict__ qkv,
     const int* __restrict__ seqlens, const float* __restrict__ lse,
     const float* __restrict__ delta, const uint32_t* __restrict__ dmask,
-    __bf16* __restrict__ dqkv, int B, int S, int NH, float p, float scale,
+    T* __restrict__ dqkv, int B, int S, int NH, float p, float scale,
     uint64_t seed, uint64_t offset) {
+  using Tr = Mfma16<T>;
+  using F8 = typename Tr::frag;
   // 4 waves x 32 q-rows (two 16-row subtiles per wave), mirroring
   // attn_fwd_kernel: K/V/K^T staged once per 128 q-rows, every staged
   // fragment feeds two independent MFMA chains.
@@ -440,10 +445,10 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
   const int g = (lane >> 4), li = lane & 15;
   const int H = NH * 64;
   const int rs3 = 3 * H;
-  const __bf16* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
-  const __bf16* kbase = qbase + H;
-  const __bf16* vbase = qbase + 2 * H;
-  const __bf16* dobase = dout + static_cast<int64_t>(b) * S * H + h * 64;
+  const T* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
+  const T* kbase = qbase + H;
+  const T* vbase = qbase + 2 * H;
+  const T* dobase = dout + static_cast<int64_t>(b) * S * H + h * 64;
   const int slen = seqlens[b];
   const float inv_keep = TRAIN_DROP ? 1.f / (1.f - p) : 1.f;
   const int Sw = (S + 31) >> 5;  // mask row stride in words
@@ -454,13 +459,13 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
   // K natural at kTrStride: serves BOTH the S^T-recompute row fragments
   // (2-way bank conflicts, tolerated) and the dQ chain's K^T fragments
   // via hardware transpose reads - no separate transposed image.
-  __bf16* K_lds = reinterpret_cast<__bf16*>(smem);   // [64][80] natural
-  __bf16* V_lds = K_lds + 64 * kTrStride;            // [64][72] natural
+  T* K_lds = reinterpret_cast<T*>(smem);   // [64][80] natural
+  T* V_lds = K_lds + 64 * kTrStride;            // [64][72] natural
   uint32_t* mk_lds = reinterpret_cast<uint32_t*>(V_lds + 64 * kStride);
 
   // this wave's two q-subtiles: Q/dO fragments + lse/delta in registers
   int q_row[2];
-  bf16x8 qfrag[2][2], dofrag[2][2];
+  F8 qfrag[2][2], dofrag[2][2];
   float lse_q[2], dlt_q[2];
 #pragma unroll
   for (int sub = 0; sub < 2; ++sub) {
@@ -519,8 +524,8 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
     // dS packs straight into its A-fragment slots (element
     // e = (t&1)*4 + r of chunk t>>1) - no [2][4][4] staging array.
     union FB {
-      bf16x8 v;
-      __bf16 e[8];
+      F8 v;
+      T e[8];
     };
     FB dsfrag[2][2];
     // (setprio brackets are inside the loops below)
@@ -538,17 +543,17 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
     }
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const __bf16* krow = &K_lds[(t * 16 + li) * kTrStride];
-      const __bf16* vrow = &V_lds[(t * 16 + li) * kStride];
-      const bf16x8 kf0 = frag_row(krow, 0, g), kf1 = frag_row(krow, 32, g);
-      const bf16x8 vf0 = frag_row(vrow, 0, g), vf1 = frag_row(vrow, 32, g);
+      const T* krow = &K_lds[(t * 16 + li) * kTrStride];
+      const T* vrow = &V_lds[(t * 16 + li) * kStride];
+      const F8 kf0 = frag_row(krow, 0, g), kf1 = frag_row(krow, 32, g);
+      const F8 vf0 = frag_row(vrow, 0, g), vf1 = frag_row(vrow, 32, g);
       f32x4 sacc[2] = {}, dpacc[2] = {};
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
-        sacc[sub] = MFMA16(kf0, qfrag[sub][0], sacc[sub]);
-        sacc[sub] = MFMA16(kf1, qfrag[sub][1], sacc[sub]);
-        dpacc[sub] = MFMA16(vf0, dofrag[sub][0], dpacc[sub]);
-        dpacc[sub] = MFMA16(vf1, dofrag[sub][1], dpacc[sub]);
+        sacc[sub] = Tr::mfma(kf0, qfrag[sub][0], sacc[sub]);
+        sacc[sub] = Tr::mfma(kf1, qfrag[sub][1], sacc[sub]);
+        dpacc[sub] = Tr::mfma(vf0, dofrag[sub][0], dpacc[sub]);
+        dpacc[sub] = Tr::mfma(vf1, dofrag[sub][1], dpacc[sub]);
       }
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
@@ -565,19 +570,19 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
             dpd = (nib >> r) & 1 ? dpd * inv_keep : 0.f;
           }
           dsfrag[sub][t >> 1].e[(t & 1) * 4 + r] =
-              __bf16(pr * (dpd - dlt_q[sub]) * scale);
+              Tr::from_f32(pr * (dpd - dlt_q[sub]) * scale);
         }
       }
     }
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-      const bf16x8 ktf0 = frag_tr(K_lds, 0, n * 16);
-      const bf16x8 ktf1 = frag_tr(K_lds, 32, n * 16);
-      acc_dq[0][n] = MFMA16(dsfrag[0][0].v, ktf0, acc_dq[0][n]);
-      acc_dq[1][n] = MFMA16(dsfrag[1][0].v, ktf0, acc_dq[1][n]);
-      acc_dq[0][n] = MFMA16(dsfrag[0][1].v, ktf1, acc_dq[0][n]);
-      acc_dq[1][n] = MFMA16(dsfrag[1][1].v, ktf1, acc_dq[1][n]);
+      const F8 ktf0 = frag_tr(K_lds, 0, n * 16);
+      const F8 ktf1 = frag_tr(K_lds, 32, n * 16);
+      acc_dq[0][n] = Tr::mfma(dsfrag[0][0].v, ktf0, acc_dq[0][n]);
+      acc_dq[1][n] = Tr::mfma(dsfrag[1][0].v, ktf0, acc_dq[1][n]);
+      acc_dq[0][n] = Tr::mfma(dsfrag[0][1].v, ktf1, acc_dq[0][n]);
+      acc_dq[1][n] = Tr::mfma(dsfrag[1][1].v, ktf1, acc_dq[1][n]);
     }
     __builtin_amdgcn_s_setprio(0);
   }
@@ -592,20 +597,22 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
         const int qr = q0 + wave * 32 + sub * 16 + g * 4 + r;
         if (qr < S) {
           dqkv[(static_cast<int64_t>(b) * S + qr) * rs3 + h * 64 + n * 16 +
-               li] = __bf16(acc_dq[sub][n][r]);
+               li] = Tr::from_f32(acc_dq[sub][n][r]);
         }
       }
     }
   }
 }
 
-template <bool TRAIN_DROP>
+template <typename T, bool TRAIN_DROP>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(
-    const __bf16* __restrict__ dout, const __bf16* __restrict__ qkv,
+    const T* __restrict__ dout, const T* __restrict__ qkv,
     const int* __restrict__ seqlens, const float* __restrict__ lse,
     const float* __restrict__ delta, const uint32_t* __restrict__ dmask,
-    __bf16* __restrict__ dqkv, int B, int S, int NH, float p, float scale,
+    T* __restrict__ dqkv, int B, int S, int NH, float p, float scale,
     uint64_t seed, uint64_t offset) {
+  using Tr = Mfma16<T>;
+  using F8 = typename Tr::frag;
   // 4 waves x 32 keys (two 16-key subtiles per wave): the heavy per-
   // q-tile staging of Q/Q^T/dO/dO^T is amortized over 128 keys, and
   // every staged Q/dO/Q^T/dO^T fragment feeds two MFMA chains.
@@ -617,10 +624,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   const int g = (lane >> 4), li = lane & 15;
   const int H = NH * 64;
   const int rs3 = 3 * H;
-  const __bf16* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
-  const __bf16* kbase = qbase + H;
-  const __bf16* vbase = qbase + 2 * H;
-  const __bf16* dobase = dout + static_cast<int64_t>(b) * S * H + h * 64;
+  const T* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
+  const T* kbase = qbase + H;
+  const T* vbase = qbase + 2 * H;
+  const T* dobase = dout + static_cast<int64_t>(b) * S * H + h * 64;
   const int slen = seqlens[b];
   const float inv_keep = TRAIN_DROP ? 1.f / (1.f - p) : 1.f;
   const int Sw = (S + 31) >> 5;  // mask row stride in words
@@ -632,10 +639,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   // 2-way conflicts) and the dK/dV chains' transposed fragments via
   // hardware transpose reads - the Qt/dOt images and their 16-scalar-
   // write-per-thread transpose scatters are gone.
-  __bf16* K_lds = reinterpret_cast<__bf16*>(smem);   // [128][72] natural
-  __bf16* V_lds = K_lds + 128 * kStride;             // [128][72] natural
-  __bf16* Q_lds = V_lds + 128 * kStride;             // [64][80] natural
-  __bf16* dO_lds = Q_lds + 64 * kTrStride;           // [64][80] natural
+  T* K_lds = reinterpret_cast<T*>(smem);   // [128][72] natural
+  T* V_lds = K_lds + 128 * kStride;             // [128][72] natural
+  T* Q_lds = V_lds + 128 * kStride;             // [64][80] natural
+  T* dO_lds = Q_lds + 64 * kTrStride;           // [64][80] natural
   float* lse_lds = reinterpret_cast<float*>(dO_lds + 64 * kTrStride);  // [64]
   float* dlt_lds = lse_lds + 64;                                      // [64]
   // keep-mask tile [64 q][128 keys] as bits, [4 words][64 q], staged per
@@ -648,7 +655,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   for (int pass = 0; pass < 2; ++pass) {
     const int row = pass * 64 + (tid >> 2), colc = (tid & 3) * 16;
     const int krow = k0 + row;
-    __bf16 kv[16], vv[16];
+    T kv[16], vv[16];
     if (krow < S) {
       const uint4* ks =
           reinterpret_cast<const uint4*>(kbase + static_cast<int64_t>(krow) * rs3 + colc);
@@ -660,7 +667,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
       *reinterpret_cast<uint4*>(&vv[8]) = vs[1];
     } else {
 #pragma unroll
-      for (int j = 0; j < 16; ++j) kv[j] = vv[j] = __bf16(0.f);
+      for (int j = 0; j < 16; ++j) kv[j] = vv[j] = Tr::from_f32(0.f);
     }
     *reinterpret_cast<uint4*>(&K_lds[row * kStride + colc]) =
         *reinterpret_cast<uint4*>(&kv[0]);
@@ -744,26 +751,26 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     // [2][4][4] staging arrays (they cost ~64 VGPRs and halved
     // occupancy at 324 VGPRs/wave)
     union FB {
-      bf16x8 v;
-      __bf16 e[8];
+      F8 v;
+      T e[8];
     };
     FB pfrag[2][2], dsfrag[2][2];
 #pragma unroll
     for (int mq = 0; mq < 4; ++mq) {
-      const __bf16* qrow_n = &Q_lds[(mq * 16 + li) * kTrStride];
-      const __bf16* dorow = &dO_lds[(mq * 16 + li) * kTrStride];
-      const bf16x8 qa0 = frag_row(qrow_n, 0, g), qa1 = frag_row(qrow_n, 32, g);
-      const bf16x8 da0 = frag_row(dorow, 0, g), da1 = frag_row(dorow, 32, g);
+      const T* qrow_n = &Q_lds[(mq * 16 + li) * kTrStride];
+      const T* dorow = &dO_lds[(mq * 16 + li) * kTrStride];
+      const F8 qa0 = frag_row(qrow_n, 0, g), qa1 = frag_row(qrow_n, 32, g);
+      const F8 da0 = frag_row(dorow, 0, g), da1 = frag_row(dorow, 32, g);
       f32x4 acc[2] = {}, dp[2] = {};
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
         const int key_local = sub ? key_local1 : key_local0;
-        const __bf16* krow_n = &K_lds[key_local * kStride];
-        const __bf16* vrow = &V_lds[key_local * kStride];
-        acc[sub] = MFMA16(qa0, frag_row(krow_n, 0, g), acc[sub]);
-        acc[sub] = MFMA16(qa1, frag_row(krow_n, 32, g), acc[sub]);
-        dp[sub] = MFMA16(da0, frag_row(vrow, 0, g), dp[sub]);
-        dp[sub] = MFMA16(da1, frag_row(vrow, 32, g), dp[sub]);
+        const T* krow_n = &K_lds[key_local * kStride];
+        const T* vrow = &V_lds[key_local * kStride];
+        acc[sub] = Tr::mfma(qa0, frag_row(krow_n, 0, g), acc[sub]);
+        acc[sub] = Tr::mfma(qa1, frag_row(krow_n, 32, g), acc[sub]);
+        dp[sub] = Tr::mfma(da0, frag_row(vrow, 0, g), dp[sub]);
+        dp[sub] = Tr::mfma(da1, frag_row(vrow, 32, g), dp[sub]);
       }
       uint32_t mrow4[4];  // keep-mask words for rows mq*16+g*4+0..3
       if (TRAIN_DROP)     // both key subtiles live in word column `wave`
@@ -789,9 +796,9 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
             dpd = keep ? dpd * inv_keep : 0.f;
             pkeep = keep ? pr * inv_keep : 0.f;  // dropped P feeds dV
           }
-          pfrag[sub][mq >> 1].e[(mq & 1) * 4 + r] = __bf16(pkeep);
+          pfrag[sub][mq >> 1].e[(mq & 1) * 4 + r] = Tr::from_f32(pkeep);
           dsfrag[sub][mq >> 1].e[(mq & 1) * 4 + r] =
-              __bf16(pr * (dpd - d_row) * scale);
+              Tr::from_f32(pr * (dpd - d_row) * scale);
         }
       }
     }
@@ -800,18 +807,18 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-      const bf16x8 dt0 = frag_tr(dO_lds, 0, m * 16);
-      const bf16x8 dt1 = frag_tr(dO_lds, 32, m * 16);
-      const bf16x8 qt0 = frag_tr(Q_lds, 0, m * 16);
-      const bf16x8 qt1 = frag_tr(Q_lds, 32, m * 16);
-      dv_acc[0][m] = MFMA16(dt0, pfrag[0][0].v, dv_acc[0][m]);
-      dv_acc[1][m] = MFMA16(dt0, pfrag[1][0].v, dv_acc[1][m]);
-      dv_acc[0][m] = MFMA16(dt1, pfrag[0][1].v, dv_acc[0][m]);
-      dv_acc[1][m] = MFMA16(dt1, pfrag[1][1].v, dv_acc[1][m]);
-      dk_acc[0][m] = MFMA16(qt0, dsfrag[0][0].v, dk_acc[0][m]);
-      dk_acc[1][m] = MFMA16(qt0, dsfrag[1][0].v, dk_acc[1][m]);
-      dk_acc[0][m] = MFMA16(qt1, dsfrag[0][1].v, dk_acc[0][m]);
-      dk_acc[1][m] = MFMA16(qt1, dsfrag[1][1].v, dk_acc[1][m]);
+      const F8 dt0 = frag_tr(dO_lds, 0, m * 16);
+      const F8 dt1 = frag_tr(dO_lds, 32, m * 16);
+      const F8 qt0 = frag_tr(Q_lds, 0, m * 16);
+      const F8 qt1 = frag_tr(Q_lds, 32, m * 16);
+      dv_acc[0][m] = Tr::mfma(dt0, pfrag[0][0].v, dv_acc[0][m]);
+      dv_acc[1][m] = Tr::mfma(dt0, pfrag[1][0].v, dv_acc[1][m]);
+      dv_acc[0][m] = Tr::mfma(dt1, pfrag[0][1].v, dv_acc[0][m]);
+      dv_acc[1][m] = Tr::mfma(dt1, pfrag[1][1].v, dv_acc[1][m]);
+      dk_acc[0][m] = Tr::mfma(qt0, dsfrag[0][0].v, dk_acc[0][m]);
+      dk_acc[1][m] = Tr::mfma(qt0, dsfrag[1][0].v, dk_acc[1][m]);
+      dk_acc[0][m] = Tr::mfma(qt1, dsfrag[0][1].v, dk_acc[0][m]);
+      dk_acc[1][m] = Tr::mfma(qt1, dsfrag[1][1].v, dk_acc[1][m]);
     }
     __builtin_amdgcn_s_setprio(0);
   }
@@ -827,8 +834,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
         const int key_abs = k0 + wave * 32 + sub * 16 + li;
         if (key_abs < S) {
           const int64_t rowb = static_cast<int64_t>(b) * S + key_abs;
-          dqkv[rowb * rs3 + H + h * 64 + dh] = __bf16(dk_acc[sub][m][r]);
-          dqkv[rowb * rs3 + 2 * H + h * 64 + dh] = __bf16(dv_acc[sub][m][r]);
+          dqkv[rowb * rs3 + H + h * 64 + dh] = Tr::from_f32(dk_acc[sub][m][r]);
+          dqkv[rowb * rs3 + 2 * H + h * 64 + dh] = Tr::from_f32(dv_acc[sub][m][r]);
         }
       }
     }
@@ -874,13 +881,12 @@ torch::Tensor tr16_probe(int64_t addr_mode) {
 // ---------------------------------------------------------------------------
 // host wrappers
 // ---------------------------------------------------------------------------
-std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
-                                         torch::Tensor seqlens,
-                                         int64_t num_heads, double p,
-                                         int64_t seed, int64_t offset) {
-  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(), "attn_fwd: bad qkv");
-  TORCH_CHECK(qkv.scalar_type() == torch::kBFloat16,
-              "attn_fwd: bf16 only (autocast path)");
+template <typename T>
+static std::vector<torch::Tensor> attention_fwd_t(torch::Tensor qkv,
+                                                  torch::Tensor seqlens,
+                                                  int64_t num_heads, double p,
+                                                  int64_t seed,
+                                                  int64_t offset) {
   const int B = qkv.size(0), S = qkv.size(1);
   const int H = qkv.size(2) / 3;
   const int NH = static_cast<int>(num_heads);
@@ -900,7 +906,7 @@ std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
   const float scale = 1.0f / sqrtf(64.f);
   auto stream = at::hip::getCurrentHIPStream();
   dim3 grid((S + 127) / 128, B * NH), block(256);  // 128 q-rows per block
-  const size_t lds = (64 * kStride + 64 * kTrStride) * sizeof(__bf16) +
+  const size_t lds = (64 * kStride + 64 * kTrStride) * sizeof(T) +
                      4 * 64 * sizeof(float) + 128 * 2 * sizeof(uint32_t);
   if (train_drop) {
     const auto [thresh, p_q] = quantize_drop_p(p);
@@ -910,10 +916,10 @@ std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
                        reinterpret_cast<uint32_t*>(dmask.data_ptr<int>()),
                        words, thresh, static_cast<uint64_t>(seed),
                        static_cast<uint64_t>(offset));
-    hipLaunchKernelGGL((attn_fwd_kernel<true>), grid, block, lds, stream,
-                       reinterpret_cast<const __bf16*>(qkv.data_ptr()),
+    hipLaunchKernelGGL((attn_fwd_kernel<T, true>), grid, block, lds, stream,
+                       reinterpret_cast<const T*>(qkv.data_ptr()),
                        seql.data_ptr<int>(),
-                       reinterpret_cast<__bf16*>(out.data_ptr()),
+                       reinterpret_cast<T*>(out.data_ptr()),
                        lse.data_ptr<float>(),
                        reinterpret_cast<const uint32_t*>(
                            dmask.data_ptr<int>()),
@@ -921,10 +927,10 @@ std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
                        static_cast<uint64_t>(seed),
                        static_cast<uint64_t>(offset));
   } else {
-    hipLaunchKernelGGL((attn_fwd_kernel<false>), grid, block, lds, stream,
-                       reinterpret_cast<const __bf16*>(qkv.data_ptr()),
+    hipLaunchKernelGGL((attn_fwd_kernel<T, false>), grid, block, lds, stream,
+                       reinterpret_cast<const T*>(qkv.data_ptr()),
                        seql.data_ptr<int>(),
-                       reinterpret_cast<__bf16*>(out.data_ptr()),
+                       reinterpret_cast<T*>(out.data_ptr()),
                        lse.data_ptr<float>(), nullptr, B, S, NH,
                        static_cast<float>(p), scale,
                        static_cast<uint64_t>(seed),
@@ -933,11 +939,27 @@ std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
   return {out, lse, dmask};
 }
 
-torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
-                            torch::Tensor seqlens, torch::Tensor out,
-                            torch::Tensor lse, torch::Tensor dmask,
-                            int64_t num_heads, double p, int64_t seed,
-                            int64_t offset) {
+// qkv [B,S,3H] bf16 or fp16 -> {out [B,S,H] same dtype, lse fp32, keep-mask}
+std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
+                                         torch::Tensor seqlens,
+                                         int64_t num_heads, double p,
+                                         int64_t seed, int64_t offset) {
+  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(), "attn_fwd: bad qkv");
+  const auto dt = qkv.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
+              "attn_fwd: qkv must be bf16 or fp16, got ", dt);
+  if (dt == torch::kHalf)
+    return attention_fwd_t<_Float16>(qkv, seqlens, num_heads, p, seed,
+                                     offset);
+  return attention_fwd_t<__bf16>(qkv, seqlens, num_heads, p, seed, offset);
+}
+
+template <typename T>
+static torch::Tensor attention_bwd_t(torch::Tensor dout, torch::Tensor qkv,
+                                     torch::Tensor seqlens, torch::Tensor out,
+                                     torch::Tensor lse, torch::Tensor dmask,
+                                     int64_t num_heads, double p,
+                                     int64_t seed, int64_t offset) {
   const int B = qkv.size(0), S = qkv.size(1);
   const int H = qkv.size(2) / 3;
   const int NH = static_cast<int>(num_heads);
@@ -950,10 +972,10 @@ torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
 
   const int64_t rows = static_cast<int64_t>(B) * NH * S;
   const int64_t delta_waves = (rows + 7) / 8;  // 8 rows per wave
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((delta_waves + 3) / 4),
+  hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((delta_waves + 3) / 4),
                      dim3(256), 0, stream,
-                     reinterpret_cast<const __bf16*>(dout_c.data_ptr()),
-                     reinterpret_cast<const __bf16*>(out.data_ptr()),
+                     reinterpret_cast<const T*>(dout_c.data_ptr()),
+                     reinterpret_cast<const T*>(out.data_ptr()),
                      delta.data_ptr<float>(), B, S, NH);
 
   dim3 grid((S + 127) / 128, B * NH), block(256);  // 128 keys per bwd block
@@ -962,15 +984,15 @@ torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
   // + 1 KB bit-mask tile -> ~59 KB (over the 64 KB default dynamic-LDS
   // cap; MI355X has 160 KB per CU)
   const size_t lds = (4 * 64 * kStride + 2 * 64 * kTrStride) *
-                         sizeof(__bf16) +
+                         sizeof(T) +
                      2 * 64 * sizeof(float) + 64 * 4 * sizeof(uint32_t);
-  const size_t lds_dq = (64 * kStride + 64 * kTrStride) * sizeof(__bf16) +
+  const size_t lds_dq = (64 * kStride + 64 * kTrStride) * sizeof(T) +
                         128 * 2 * sizeof(uint32_t);
   HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&attn_bwd_kernel<true>),
+      reinterpret_cast<const void*>(&attn_bwd_kernel<T, true>),
       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&attn_bwd_kernel<false>),
+      reinterpret_cast<const void*>(&attn_bwd_kernel<T, false>),
       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   const float scale = 1.0f / sqrtf(64.f);
   const bool train_drop = p > 0.0;
@@ -982,23 +1004,45 @@ torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
                  : nullptr;
   auto args = [&](auto kernel, dim3 g, size_t lds_bytes) {
     hipLaunchKernelGGL(kernel, g, block, lds_bytes, stream,
-                       reinterpret_cast<const __bf16*>(dout_c.data_ptr()),
-                       reinterpret_cast<const __bf16*>(qkv.data_ptr()),
+                       reinterpret_cast<const T*>(dout_c.data_ptr()),
+                       reinterpret_cast<const T*>(qkv.data_ptr()),
                        seql.data_ptr<int>(), lse.data_ptr<float>(),
                        delta.data_ptr<float>(), mask_ptr,
-                       reinterpret_cast<__bf16*>(dqkv.data_ptr()), B, S, NH,
+                       reinterpret_cast<T*>(dqkv.data_ptr()), B, S, NH,
                        p_q, scale,
                        static_cast<uint64_t>(seed),
                        static_cast<uint64_t>(offset));
   };
   if (train_drop) {
-    args(attn_bwd_kernel<true>, grid, lds);
-    args(attn_dq_kernel<true>, grid_dq, lds_dq);
+    args(attn_bwd_kernel<T, true>, grid, lds);
+    args(attn_dq_kernel<T, true>, grid_dq, lds_dq);
   } else {
-    args(attn_bwd_kernel<false>, grid, lds);
-    args(attn_dq_kernel<false>, grid_dq, lds_dq);
+    args(attn_bwd_kernel<T, false>, grid, lds);
+    args(attn_dq_kernel<T, false>, grid_dq, lds_dq);
   }
   return dqkv;
+}
+
+// dout/qkv/out must share one dtype (bf16 or fp16); checked before any
+// launch so a mixed call cannot reinterpret one operand's bits.
+torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
+                            torch::Tensor seqlens, torch::Tensor out,
+                            torch::Tensor lse, torch::Tensor dmask,
+                            int64_t num_heads, double p, int64_t seed,
+                            int64_t offset) {
+  const auto dt = qkv.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
+              "attn_bwd: qkv must be bf16 or fp16, got ", dt);
+  TORCH_CHECK(dout.scalar_type() == dt,
+              "attn_bwd: dout dtype ", dout.scalar_type(),
+              " does not match qkv dtype ", dt);
+  TORCH_CHECK(out.scalar_type() == dt, "attn_bwd: out dtype ",
+              out.scalar_type(), " does not match qkv dtype ", dt);
+  if (dt == torch::kHalf)
+    return attention_bwd_t<_Float16>(dout, qkv, seqlens, out, lse, dmask,
+                                     num_heads, p, seed, offset);
+  return attention_bwd_t<__bf16>(dout, qkv, seqlens, out, lse, dmask,
+                                 num_heads, p, seed, offset);
 }
 
 }  // namespace bpa

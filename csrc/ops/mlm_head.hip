@@ -33,23 +33,19 @@
 //
 // Numerics: fp32 MFMA accumulation; the CE statistics are computed
 // from the bf16-ROUNDED logits (exactly the values backward re-reads),
-// so forward lse and backward softmax see identical inputs.
+// so forward lse and backward softmax see identical inputs. The
+// kernels are templated on the 16-bit element type (csrc/mfma_types.h):
+// with fp16 inputs the logits are fp16 and "bf16" above reads "fp16".
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 #include "../common.h"
+#include "../mfma_types.h"
 
 namespace bpa {
 
 namespace mh {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4v;
-
-#define MFMA16(A, B, C) \
-  __builtin_amdgcn_mfma_f32_16x16x32_bf16((A), (B), (C), 0, 0, 0)
 
 constexpr int kBM = 256;  // h-rows per block
 constexpr int kBN = 256;  // vocab columns per block (4 x 64 stripes)
@@ -65,36 +61,40 @@ __device__ __forceinline__ int swz_off(int r, int k) {
 
 // fragment for MFMA depth base ks (0 or 32): lane (g = lane>>4,
 // li = lane&15) holds row rb+li, k = ks+4g..+3 and ks+16+4g..+3 (the
-// probe-verified gfx950 16x16x32 layout).
-__device__ __forceinline__ bf16x8 frag_k(const char* img, int rb, int ks) {
+// probe-verified gfx950 16x16x32 layout, shared by the bf16 and f16
+// instructions). T is the 16-bit element type (csrc/mfma_types.h).
+template <typename T>
+__device__ __forceinline__ typename Mfma16<T>::frag frag_k(const char* img,
+                                                           int rb, int ks) {
+  using Tr = Mfma16<T>;
+  using H4 = typename Tr::tr4;  // plain 8-byte chunk here, no transpose
   const int lane = threadIdx.x & 63;
   const int g = (lane >> 4) & 3, li = lane & 15;
   const int r = rb + li;
   union {
-    bf16x8 v;
-    bf16x4v h[2];
+    typename Tr::frag v;
+    H4 h[2];
   } f;
-  f.h[0] = *reinterpret_cast<const bf16x4v*>(img + swz_off(r, ks + 4 * g));
-  f.h[1] =
-      *reinterpret_cast<const bf16x4v*>(img + swz_off(r, ks + 16 + 4 * g));
+  f.h[0] = *reinterpret_cast<const H4*>(img + swz_off(r, ks + 4 * g));
+  f.h[1] = *reinterpret_cast<const H4*>(img + swz_off(r, ks + 16 + 4 * g));
   return f.v;
 }
 
 }  // namespace mh
 
-using mh::bf16x8;
-using mh::f32x4;
-
 // grid: (P/256, ceil(V/256)); 512 threads = 8 waves as 2(M) x 4(N),
 // each wave a 128x64 sub-tile. The wave's 64-col stripe is also the
 // CE-partial granule, so row statistics never cross waves.
+template <typename T>
 __global__ __launch_bounds__(512) void mlm_fwd_kernel(
-    const __bf16* __restrict__ h,     // [P, K]
-    const __bf16* __restrict__ w,     // [V, K]
+    const T* __restrict__ h,     // [P, K]
+    const T* __restrict__ w,     // [V, K]
     const float* __restrict__ bias,   // [V]
-    __bf16* __restrict__ logits,      // [P, V]
+    T* __restrict__ logits,      // [P, V]
     float* __restrict__ part,         // [P, nStripes, 2] (max, sumexp)
     int P, int V, int K, int nStripes) {
+  using Tr = Mfma16<T>;
+  using F8 = typename Tr::frag;
   const int m0 = blockIdx.x * mh::kBM;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -126,7 +126,7 @@ __global__ __launch_bounds__(512) void mlm_fwd_kernel(
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       const int r = wave * 32 + c * 8 + st_sub;  // 0..255
-      const __bf16* ga =
+      const T* ga =
           h + static_cast<int64_t>(m0 + r) * K + k0 + st_swz;
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)ga,
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(512) void mlm_fwd_kernel(
                                                         128),
           16, 0, 0);
       // vocab tail: clamp W row (always-legal; epilogue masks)
-      const __bf16* gw =
+      const T* gw =
           w + static_cast<int64_t>(min(n0 + r, V - 1)) * K + k0 + st_swz;
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)gw,
@@ -157,17 +157,17 @@ __global__ __launch_bounds__(512) void mlm_fwd_kernel(
     const char* wt = at + mh::kATileB;
 #pragma unroll
     for (int kd = 0; kd < 2; ++kd) {  // two MFMA depths per staged tile
-      bf16x8 bfr[4];
+      F8 bfr[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        bfr[t] = mh::frag_k(wt, wj * 64 + t * 16, kd * 32);
+        bfr[t] = mh::frag_k<T>(wt, wj * 64 + t * 16, kd * 32);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ti = 0; ti < 8; ++ti) {
-        const bf16x8 af = mh::frag_k(at, wi * 128 + ti * 16, kd * 32);
+        const F8 af = mh::frag_k<T>(at, wi * 128 + ti * 16, kd * 32);
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj)
-          acc[ti][tj] = MFMA16(af, bfr[tj], acc[ti][tj]);
+          acc[ti][tj] = Tr::mfma(af, bfr[tj], acc[ti][tj]);
       }
       __builtin_amdgcn_s_setprio(0);
     }
@@ -187,9 +187,9 @@ __global__ __launch_bounds__(512) void mlm_fwd_kernel(
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj) {
           const int nj = nw0 + tj * 16 + li;
-          const __bf16 ob = __bf16(acc[ti][tj][r] + bv[tj]);
+          const T ob = Tr::from_f32(acc[ti][tj][r] + bv[tj]);
           logits[static_cast<int64_t>(mi) * V + nj] = ob;
-          const float f = static_cast<float>(ob);
+          const float f = Tr::to_f32(ob);
           if (f > mx) {
             sx *= __expf(mx - f);
             mx = f;
@@ -200,10 +200,10 @@ __global__ __launch_bounds__(512) void mlm_fwd_kernel(
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj) {
           const int nj = nw0 + tj * 16 + li;
-          const __bf16 ob = __bf16(acc[ti][tj][r] + bv[tj]);
+          const T ob = Tr::from_f32(acc[ti][tj][r] + bv[tj]);
           if (cv[tj]) {
             logits[static_cast<int64_t>(mi) * V + nj] = ob;
-            const float f = static_cast<float>(ob);
+            const float f = Tr::to_f32(ob);
             if (f > mx) {
               sx *= __expf(mx - f);
               mx = f;
@@ -235,8 +235,9 @@ __global__ __launch_bounds__(512) void mlm_fwd_kernel(
 
 // fold per-row partials -> lse, loss: one wave per row (4 rows per
 // block), coalesced 8-B lane reads over the stripe partials.
+template <typename T>
 __global__ void mlm_fold_kernel(const float* __restrict__ part,
-                                const __bf16* __restrict__ logits,
+                                const T* __restrict__ logits,
                                 const int64_t* __restrict__ labels,
                                 float* __restrict__ row_out,  // [2, rows]
                                 float* __restrict__ lse_out, int rows,
@@ -269,7 +270,7 @@ __global__ void mlm_fold_kernel(const float* __restrict__ part,
     // per-row (loss, valid) instead of same-address atomics (2 x rows
     // serialized L2 atomics); mlm_sum_kernel folds them
     const bool valid = label != ignore_index;
-    const float xl = valid ? static_cast<float>(
+    const float xl = valid ? Mfma16<T>::to_f32(
                                  logits[static_cast<int64_t>(row) * V +
                                         (valid ? label : 0)])
                            : 0.f;
@@ -307,21 +308,12 @@ bool mlm_head_supported(int64_t P, int64_t V, int64_t K) {
   return P % mh::kBM == 0 && K % mh::kBK == 0 && K >= 64 && V >= 2;
 }
 
-// h [P,K] bf16, w [V,K] bf16, bias [V] fp32, labels [P] int64 ->
-// {logits [P,V] bf16, loss_sum f32, count f32, lse [P] f32}
-std::vector<torch::Tensor> mlm_head_fwd(torch::Tensor h, torch::Tensor w,
-                                        torch::Tensor bias,
-                                        torch::Tensor labels,
-                                        int64_t ignore_index) {
-  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() &&
-                  h.scalar_type() == torch::kBFloat16,
-              "mlm_head_fwd: h must be contiguous 2D bf16");
-  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() &&
-                  w.scalar_type() == torch::kBFloat16,
-              "mlm_head_fwd: w must be contiguous 2D bf16");
-  TORCH_CHECK(bias.is_cuda() && bias.dim() == 1 &&
-                  bias.scalar_type() == torch::kFloat32,
-              "mlm_head_fwd: bias must be 1D fp32");
+template <typename T>
+static std::vector<torch::Tensor> mlm_head_fwd_t(torch::Tensor h,
+                                                 torch::Tensor w,
+                                                 torch::Tensor bias,
+                                                 torch::Tensor labels,
+                                                 int64_t ignore_index) {
   const int P = h.size(0), K = h.size(1), V = w.size(0);
   TORCH_CHECK(w.size(1) == K && bias.size(0) == V,
               "mlm_head_fwd: shape mismatch");
@@ -340,24 +332,47 @@ std::vector<torch::Tensor> mlm_head_fwd(torch::Tensor h, torch::Tensor w,
 
   const size_t lds = 2 * mh::kBufB;
   HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&mlm_fwd_kernel),
+      reinterpret_cast<const void*>(&mlm_fwd_kernel<T>),
       hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  hipLaunchKernelGGL(mlm_fwd_kernel,
+  hipLaunchKernelGGL(mlm_fwd_kernel<T>,
                      dim3(P / mh::kBM, (V + mh::kBN - 1) / mh::kBN),
                      dim3(512), lds, stream,
-                     reinterpret_cast<const __bf16*>(h.data_ptr()),
-                     reinterpret_cast<const __bf16*>(w.data_ptr()),
+                     reinterpret_cast<const T*>(h.data_ptr()),
+                     reinterpret_cast<const T*>(w.data_ptr()),
                      bias.data_ptr<float>(),
-                     reinterpret_cast<__bf16*>(logits.data_ptr()),
+                     reinterpret_cast<T*>(logits.data_ptr()),
                      part.data_ptr<float>(), P, V, K, nStripes);
-  hipLaunchKernelGGL(mlm_fold_kernel, dim3((P + 3) / 4), dim3(256), 0,
+  hipLaunchKernelGGL(mlm_fold_kernel<T>, dim3((P + 3) / 4), dim3(256), 0,
                      stream, part.data_ptr<float>(),
-                     reinterpret_cast<const __bf16*>(logits.data_ptr()),
+                     reinterpret_cast<const T*>(logits.data_ptr()),
                      labels_c.data_ptr<int64_t>(), row_out.data_ptr<float>(),
                      lse.data_ptr<float>(), P, nStripes, V, ignore_index);
   hipLaunchKernelGGL(mlm_sum_kernel, dim3(1), dim3(256), 0, stream,
                      row_out.data_ptr<float>(), sums.data_ptr<float>(), P);
   return {logits, sums.select(0, 0), sums.select(0, 1), lse};
+}
+
+// h [P,K] and w [V,K] both bf16 or both fp16, bias [V] fp32, labels [P]
+// int64 -> {logits [P,V] in the input dtype, loss_sum f32, count f32,
+// lse [P] f32}
+std::vector<torch::Tensor> mlm_head_fwd(torch::Tensor h, torch::Tensor w,
+                                        torch::Tensor bias,
+                                        torch::Tensor labels,
+                                        int64_t ignore_index) {
+  const auto dt = h.scalar_type();
+  TORCH_CHECK(h.is_cuda() && h.dim() == 2 && h.is_contiguous() &&
+                  (dt == torch::kBFloat16 || dt == torch::kHalf),
+              "mlm_head_fwd: h must be contiguous 2D bf16 or fp16");
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous(),
+              "mlm_head_fwd: w must be contiguous 2D");
+  TORCH_CHECK(w.scalar_type() == dt, "mlm_head_fwd: w dtype ",
+              w.scalar_type(), " does not match h dtype ", dt);
+  TORCH_CHECK(bias.is_cuda() && bias.dim() == 1 &&
+                  bias.scalar_type() == torch::kFloat32,
+              "mlm_head_fwd: bias must be 1D fp32");
+  if (dt == torch::kHalf)
+    return mlm_head_fwd_t<_Float16>(h, w, bias, labels, ignore_index);
+  return mlm_head_fwd_t<__bf16>(h, w, bias, labels, ignore_index);
 }
 
 }  // namespace bpa

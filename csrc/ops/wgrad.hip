@@ -1,6 +1,7 @@
 // Hand-written split-K MFMA weight-gradient GEMM for MI355X (gfx950).
 //
-// dW[M,N] = dy^T @ x with dy [K,M] and x [K,N] row-major bf16 (the
+// dW[M,N] = dy^T @ x with dy [K,M] and x [K,N] row-major bf16 or fp16
+// (kernels templated on the element type, csrc/mfma_types.h) (the
 // "TN" wgrad form of every encoder linear: QKV [3072,1024], attn-out
 // [1024,1024], FFN1 [4096,1024], FFN2 [1024,4096] at K = B*S tokens).
 // hipBLASLt/rocBLAS top out at ~580-790 TF/s on these shapes even
@@ -31,18 +32,11 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "../common.h"
+#include "../mfma_types.h"
 
 namespace bpa {
 
 namespace wg {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4v;
-typedef __attribute__((address_space(3))) bf16x4v* lds_bf16x4p;
-
-#define MFMA16(A, B, C) \
-  __builtin_amdgcn_mfma_f32_16x16x32_bf16((A), (B), (C), 0, 0, 0)
 
 constexpr int kBM = 128;   // C tile rows (M)
 constexpr int kBN = 128;   // C tile cols (N)
@@ -50,38 +44,39 @@ constexpr int kBK = 32;    // K step (32-deep: 36.8 KB LDS -> 4 blocks/CU)
 constexpr int kStride = 144;  // LDS row stride (elems), tr-conflict-free
 
 // Transposed fragment from a natural [kBK][cols] row-major LDS image at
-// stride kStride: element e = img[rb + g*4 + (e&3) + 16*(e>>2)][cb+li].
-__device__ __forceinline__ bf16x8 frag_tr(const __bf16* img, int rb,
-                                          int cb) {
+// row stride STRIDE: element e = img[rb + g*4 + (e&3) + 16*(e>>2)][cb+li].
+// T is the 16-bit element type (__bf16 or _Float16, csrc/mfma_types.h).
+template <int STRIDE, typename T>
+__device__ __forceinline__ typename Mfma16<T>::frag frag_tr(const T* img,
+                                                            int rb, int cb) {
+  using Tr = Mfma16<T>;
   const int lane = threadIdx.x & 63;
   const int g = (lane >> 4) & 3, t = lane & 15;
-  const __bf16* p0 =
-      img + (rb + g * 4 + (t >> 2)) * kStride + cb + (t & 3) * 4;
+  const T* p0 =
+      img + (rb + g * 4 + (t >> 2)) * STRIDE + cb + (t & 3) * 4;
   union {
-    bf16x8 v;
-    bf16x4v h[2];
+    typename Tr::frag v;
+    typename Tr::tr4 h[2];
   } r;
-  r.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4p)(p0));
-  r.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4p)(p0 + 16 * kStride));
+  r.h[0] = Tr::tr_read(p0);
+  r.h[1] = Tr::tr_read(p0 + 16 * STRIDE);
   return r.v;
 }
 
 }  // namespace wg
 
-using wg::bf16x8;
-using wg::f32x4;
-
 // grid: (M/128, N/128, splitk); block 256. BK = 32 or 64: 64 halves
 // the barrier count and doubles the MFMA run per staged tile (36.8 ->
 // 73.7 KB LDS, 4 -> 2 blocks/CU); which wins is per-shape (sweep in
 // benchmarks/wgrad_sweep.py) and picked by the host wrapper.
-template <int BK>
+template <typename T, int BK>
 __global__ __launch_bounds__(256) void wgrad_tn_kernel(
-    const __bf16* __restrict__ dy,  // [K, M]
-    const __bf16* __restrict__ x,   // [K, N]
+    const T* __restrict__ dy,  // [K, M]
+    const T* __restrict__ x,   // [K, N]
     float* __restrict__ part,       // [splitk, M, N]
     int K, int M, int N, int k_slice) {
+  using Tr = Mfma16<T>;
+  using F8 = typename Tr::frag;
   const int m0 = blockIdx.x * wg::kBM;
   const int n0 = blockIdx.y * wg::kBN;
   const int kz0 = blockIdx.z * k_slice;
@@ -96,7 +91,7 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(
   // flat_store for the staging writes (observed in the .s; 2-3x the
   // ds_write cost plus per-store 64-bit compares)
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* lds = reinterpret_cast<__bf16*>(smem);
+  T* lds = reinterpret_cast<T*>(smem);
   constexpr int kTile = BK * wg::kStride;
   constexpr int kTPR = 256 / BK;      // staging threads per k-row
   constexpr int kSlots = BK / 16;     // uint4 slots per thread per matrix
@@ -149,23 +144,23 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(
     __syncthreads();
     issue_loads(k0 + BK < kz1 ? k0 + BK : k0);  // T14 issue-early
 
-    const __bf16* dyt = lds + boff;
-    const __bf16* xt = lds + boff + kTile;
+    const T* dyt = lds + boff;
+    const T* xt = lds + boff + kTile;
 #pragma unroll
     for (int kd = 0; kd < BK / 32; ++kd) {
-      bf16x8 af[4], bfr[4];
+      F8 af[4], bfr[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        af[t] = wg::frag_tr(dyt, kd * 32, wi * 64 + t * 16);
+        af[t] = wg::frag_tr<wg::kStride>(dyt, kd * 32, wi * 64 + t * 16);
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        bfr[t] = wg::frag_tr(xt, kd * 32, wj * 64 + t * 16);
+        bfr[t] = wg::frag_tr<wg::kStride>(xt, kd * 32, wj * 64 + t * 16);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ti = 0; ti < 4; ++ti)
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj)
-          acc[ti][tj] = MFMA16(af[ti], bfr[tj], acc[ti][tj]);
+          acc[ti][tj] = Tr::mfma(af[ti], bfr[tj], acc[ti][tj]);
       __builtin_amdgcn_s_setprio(0);
     }
     // no trailing barrier: the next iteration writes the OTHER buffer,
@@ -198,11 +193,14 @@ namespace wg {
 constexpr int kStride256 = 272;  // 136 dw: 8r+2c covers even banks once
 }
 
+template <typename T>
 __global__ __launch_bounds__(512) void wgrad_tn256_kernel(
-    const __bf16* __restrict__ dy,  // [K, M]
-    const __bf16* __restrict__ x,   // [K, N]
+    const T* __restrict__ dy,  // [K, M]
+    const T* __restrict__ x,   // [K, N]
     float* __restrict__ part,       // [splitk, M, N]
     int K, int M, int N, int k_slice) {
+  using Tr = Mfma16<T>;
+  using F8 = typename Tr::frag;
   const int m0 = blockIdx.x * 256;
   const int n0 = blockIdx.y * 256;
   const int kz0 = blockIdx.z * k_slice;
@@ -213,7 +211,7 @@ __global__ __launch_bounds__(512) void wgrad_tn256_kernel(
   const int g = (lane >> 4), li = lane & 15;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __bf16* lds = reinterpret_cast<__bf16*>(smem);
+  T* lds = reinterpret_cast<T*>(smem);
   constexpr int kTile = wg::kBK * wg::kStride256;
 
   // staging: 32 rows x 256 cols = 16 bf16 per thread per matrix
@@ -255,47 +253,21 @@ __global__ __launch_bounds__(512) void wgrad_tn256_kernel(
     __syncthreads();
     issue_loads(k0 + wg::kBK < kz1 ? k0 + wg::kBK : k0);
 
-    const __bf16* dyt = lds + boff;
-    const __bf16* xt = lds + boff + kTile;
+    const T* dyt = lds + boff;
+    const T* xt = lds + boff + kTile;
     {
-      bf16x8 bfr[4];
+      F8 bfr[4];
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int lane2 = threadIdx.x & 63;
-        const int gg = (lane2 >> 4) & 3, tt = lane2 & 15;
-        const __bf16* p0 = xt +
-            (gg * 4 + (tt >> 2)) * wg::kStride256 + wj * 64 + t * 16 +
-            (tt & 3) * 4;
-        union {
-          bf16x8 v;
-          wg::bf16x4v h[2];
-        } r;
-        r.h[0] =
-            __builtin_amdgcn_ds_read_tr16_b64_v4bf16((wg::lds_bf16x4p)(p0));
-        r.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-            (wg::lds_bf16x4p)(p0 + 16 * wg::kStride256));
-        bfr[t] = r.v;
-      }
+      for (int t = 0; t < 4; ++t)
+        bfr[t] = wg::frag_tr<wg::kStride256>(xt, 0, wj * 64 + t * 16);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ti = 0; ti < 8; ++ti) {
-        const int lane2 = threadIdx.x & 63;
-        const int gg = (lane2 >> 4) & 3, tt = lane2 & 15;
-        const __bf16* p0 = dyt +
-            (gg * 4 + (tt >> 2)) * wg::kStride256 + wi * 128 + ti * 16 +
-            (tt & 3) * 4;
-        union {
-          bf16x8 v;
-          wg::bf16x4v h[2];
-        } r;
-        r.h[0] =
-            __builtin_amdgcn_ds_read_tr16_b64_v4bf16((wg::lds_bf16x4p)(p0));
-        r.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-            (wg::lds_bf16x4p)(p0 + 16 * wg::kStride256));
-        const bf16x8 af = r.v;
+        const F8 af =
+            wg::frag_tr<wg::kStride256>(dyt, 0, wi * 128 + ti * 16);
 #pragma unroll
         for (int tj = 0; tj < 4; ++tj)
-          acc[ti][tj] = MFMA16(af, bfr[tj], acc[ti][tj]);
+          acc[ti][tj] = Tr::mfma(af, bfr[tj], acc[ti][tj]);
       }
       __builtin_amdgcn_s_setprio(0);
     }
@@ -317,10 +289,15 @@ __global__ __launch_bounds__(512) void wgrad_tn256_kernel(
   }
 }
 
-// part [S, M, N] fp32 -> out [M, N] bf16 (sum over S)
+// part [S, M, N] fp32 -> out [M, N] bf16/fp16 (sum over S). The final
+// narrowing rounds to nearest-even; for fp16 a sum beyond +-65504
+// becomes +-inf, never a clamped finite value (the GradScaler's
+// overflow detection depends on it).
+template <typename T>
 __global__ void wgrad_combine_kernel(const float* __restrict__ part,
-                                     __bf16* __restrict__ out, int splitk,
+                                     T* __restrict__ out, int splitk,
                                      int64_t mn) {
+  using Tr = Mfma16<T>;
   const int64_t i =
       (static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x) * 4;
   if (i >= mn) return;
@@ -331,9 +308,9 @@ __global__ void wgrad_combine_kernel(const float* __restrict__ part,
 #pragma unroll
     for (int k = 0; k < 4; ++k) s[k] += p[k];
   }
-  __bf16 o[4];
+  T o[4];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) o[k] = __bf16(s[k]);
+  for (int k = 0; k < 4; ++k) o[k] = Tr::from_f32(s[k]);
   *reinterpret_cast<uint2*>(out + i) = *reinterpret_cast<uint2*>(o);
 }
 
@@ -351,15 +328,9 @@ bool wgrad_tn_profitable(int64_t K, int64_t M, int64_t N) {
          M <= 8192 && K >= 4096;
 }
 
-// dW = dy^T @ x; dy [K,M] bf16 row-major contiguous, x [K,N] likewise.
-torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x,
-                       int64_t splitk_override) {
-  TORCH_CHECK(dy.is_cuda() && dy.dim() == 2 && dy.is_contiguous() &&
-                  dy.scalar_type() == torch::kBFloat16,
-              "wgrad_tn: dy must be contiguous 2D bf16");
-  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
-                  x.scalar_type() == torch::kBFloat16,
-              "wgrad_tn: x must be contiguous 2D bf16");
+template <typename T>
+static torch::Tensor wgrad_tn_t(torch::Tensor dy, torch::Tensor x,
+                                int64_t splitk_override) {
   const int K = dy.size(0), M = dy.size(1), N = x.size(1);
   TORCH_CHECK(x.size(0) == K, "wgrad_tn: K mismatch");
   TORCH_CHECK(wgrad_tn_supported(K, M, N), "wgrad_tn: unsupported shape");
@@ -389,37 +360,53 @@ torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x,
   auto stream = at::hip::getCurrentHIPStream();
   dim3 grid(M / bm, N / bn, splitk), block(big ? 512 : 256);
   const size_t lds =
-      4 * bk * (big ? wg::kStride256 : wg::kStride) * sizeof(__bf16);
+      4 * bk * (big ? wg::kStride256 : wg::kStride) * sizeof(T);
   if (big) {
     HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_tn256_kernel),
+        reinterpret_cast<const void*>(&wgrad_tn256_kernel<T>),
         hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(wgrad_tn256_kernel, grid, block, lds, stream,
-                       reinterpret_cast<const __bf16*>(dy.data_ptr()),
-                       reinterpret_cast<const __bf16*>(x.data_ptr()),
+    hipLaunchKernelGGL(wgrad_tn256_kernel<T>, grid, block, lds, stream,
+                       reinterpret_cast<const T*>(dy.data_ptr()),
+                       reinterpret_cast<const T*>(x.data_ptr()),
                        part.data_ptr<float>(), K, M, N, k_slice);
   } else if (bk == 64) {
     HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_tn_kernel<64>),
+        reinterpret_cast<const void*>(&wgrad_tn_kernel<T, 64>),
         hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(wgrad_tn_kernel<64>, grid, block, lds, stream,
-                       reinterpret_cast<const __bf16*>(dy.data_ptr()),
-                       reinterpret_cast<const __bf16*>(x.data_ptr()),
+    hipLaunchKernelGGL((wgrad_tn_kernel<T, 64>), grid, block, lds, stream,
+                       reinterpret_cast<const T*>(dy.data_ptr()),
+                       reinterpret_cast<const T*>(x.data_ptr()),
                        part.data_ptr<float>(), K, M, N, k_slice);
   } else {
     HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_tn_kernel<32>),
+        reinterpret_cast<const void*>(&wgrad_tn_kernel<T, 32>),
         hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(wgrad_tn_kernel<32>, grid, block, lds, stream,
-                       reinterpret_cast<const __bf16*>(dy.data_ptr()),
-                       reinterpret_cast<const __bf16*>(x.data_ptr()),
+    hipLaunchKernelGGL((wgrad_tn_kernel<T, 32>), grid, block, lds, stream,
+                       reinterpret_cast<const T*>(dy.data_ptr()),
+                       reinterpret_cast<const T*>(x.data_ptr()),
                        part.data_ptr<float>(), K, M, N, k_slice);
   }
   const int64_t mn = static_cast<int64_t>(M) * N;
-  hipLaunchKernelGGL(wgrad_combine_kernel, dim3((mn / 4 + 255) / 256),
+  hipLaunchKernelGGL(wgrad_combine_kernel<T>, dim3((mn / 4 + 255) / 256),
                      dim3(256), 0, stream, part.data_ptr<float>(),
-                     reinterpret_cast<__bf16*>(out.data_ptr()), splitk, mn);
+                     reinterpret_cast<T*>(out.data_ptr()), splitk, mn);
   return out;
+}
+
+// dW = dy^T @ x; dy [K,M] row-major contiguous, x [K,N] likewise, both
+// bf16 or both fp16; dW comes back in the same dtype.
+torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x,
+                       int64_t splitk_override) {
+  const auto dt = dy.scalar_type();
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 2 && dy.is_contiguous() &&
+                  (dt == torch::kBFloat16 || dt == torch::kHalf),
+              "wgrad_tn: dy must be contiguous 2D bf16 or fp16");
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous(),
+              "wgrad_tn: x must be contiguous 2D");
+  TORCH_CHECK(x.scalar_type() == dt, "wgrad_tn: x dtype ", x.scalar_type(),
+              " does not match dy dtype ", dt);
+  if (dt == torch::kHalf) return wgrad_tn_t<_Float16>(dy, x, splitk_override);
+  return wgrad_tn_t<__bf16>(dy, x, splitk_override);
 }
 
 }  // namespace bpa

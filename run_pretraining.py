@@ -79,7 +79,9 @@ def parse_arguments(args=None) -> argparse.Namespace:
                              "instead of fp32 weights + autocast")
     parser.add_argument("--seed", type=int, default=42)
     parser.add_argument("--fp16", action="store_true",
-                        help="fp16 autocast + dynamic GradScaler")
+                        help="fp16 autocast + dynamic GradScaler (attention, "
+                             "wgrad and the MLM head run their native fp16 "
+                             "MFMA kernels)")
     parser.add_argument("--bf16", action="store_true",
                         help="bf16 autocast (MI355X-preferred; wins over --fp16)")
     parser.add_argument("--num_steps_per_checkpoint", type=int, default=200)
