@@ -14,6 +14,11 @@ encoder shapes next to the library's ``dy.t() @ x``, MLM head). With
 several ``--dtype`` values and ``--repeats N`` the dtypes alternate
 inside each repeat, so fp16 is compared with the bf16 run-to-run spread
 of the same process; a final summary line per op gives min/median/max.
+
+``--section varlen`` times variable-length (packed) attention against
+padded attention at B=16,S=512 and B=32,S=128 for the length
+distributions of benchmarks/unpad_bench.py, forward and backward, with
+and without dropout; the two kernels alternate inside each repeat.
 """
 
 from __future__ import annotations
@@ -158,19 +163,98 @@ def bench_mfma(phase, dtypes, repeats):
         }), flush=True)
 
 
+def bench_varlen(dtypes, repeats):
+    """attention_varlen_fwd/bwd next to attention_fwd/bwd on the same
+    sequences: the padded call sees [B,S,3H] and per-sequence lengths,
+    the packed call the valid rows only and cu_seqlens."""
+    from unpad_bench import DISTRIBUTIONS, SHAPES, make_lengths
+
+    dev = torch.device("cuda:0")
+    ext = ops.extension()
+    H, NH = 1024, 16
+    samples = {}
+
+    def timeit_long(fn):
+        return timeit(fn, iters=200, warmup=20)
+
+    def rec(name, us, extra):
+        report(name, us, 0, extra)
+        samples.setdefault(name, []).append(us)
+
+    for dname in dtypes:
+        dt = DTYPES[dname]
+        for b, s in SHAPES:
+            for dist in DISTRIBUTIONS:
+                torch.manual_seed(0)
+                lengths = make_lengths(dist, b, s)
+                total = int(lengths.sum())
+                t_pad = -(-total // 128) * 128
+                cu = torch.zeros(b + 1, dtype=torch.int32)
+                cu[1:] = torch.cumsum(lengths, 0)
+                cu = cu.to(dev)
+                seqlens = lengths.to(dev, torch.int32)
+                qkv_p = (torch.randn(b, s, 3 * H, device=dev) * 0.5).to(dt)
+                do_p = (torch.randn(b, s, H, device=dev) * 0.5).to(dt)
+                qkv_v = (torch.randn(t_pad, 3 * H, device=dev) * 0.5).to(dt)
+                do_v = (torch.randn(t_pad, H, device=dev) * 0.5).to(dt)
+                # useful work: the valid [len, len] score blocks only
+                aflops = 4 * NH * 64 * int((lengths * lengths).sum())
+                info = {"pad_frac": round(1 - total / (b * s), 3)}
+                for _ in range(repeats):
+                    for p_drop, sfx in ((0.0, ""), (0.1, "_drop")):
+                        tag = f"B{b}_S{s}_{dist}{sfx}[{dname}]"
+                        calls = {
+                            "padded": (
+                                lambda: ext.attention_fwd(
+                                    qkv_p, seqlens, NH, p_drop, 7, 0),
+                                lambda o, l, m: ext.attention_bwd(
+                                    do_p, qkv_p, seqlens, o, l, m, NH,
+                                    p_drop, 7, 0),
+                            ),
+                            "varlen": (
+                                lambda: ext.attention_varlen_fwd(
+                                    qkv_v, cu, s, NH, p_drop, 7, 0),
+                                lambda o, l, m: ext.attention_varlen_bwd(
+                                    do_v, qkv_v, cu, s, o, l, m, NH,
+                                    p_drop, 7, 0),
+                            ),
+                        }
+                        for kind, (fwd, bwd) in calls.items():
+                            us = timeit_long(fwd)
+                            rec(f"attn_{kind}_fwd_{tag}", us, dict(
+                                info, useful_TFLOP_s=round(
+                                    aflops / (us * 1e-6) / 1e12, 1)))
+                            o, l, m = fwd()
+                            us = timeit_long(lambda: bwd(o, l, m))
+                            rec(f"attn_{kind}_bwd_{tag}", us, dict(
+                                info, useful_TFLOP_s=round(
+                                    2.5 * aflops / (us * 1e-6) / 1e12, 1)))
+
+    for name, v in samples.items():
+        v = sorted(v)
+        print(json.dumps({
+            "summary": name, "n": len(v), "min_us": round(v[0], 2),
+            "median_us": round(v[len(v) // 2], 2),
+            "max_us": round(v[-1], 2),
+        }), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--phase", type=int, default=1, choices=[1, 2])
     p.add_argument("--dtype", nargs="+", default=["bf16"],
                    choices=sorted(DTYPES),
                    help="16-bit element type(s); --section all uses the first")
-    p.add_argument("--section", default="all", choices=["all", "mfma"])
+    p.add_argument("--section", default="all", choices=["all", "mfma", "varlen"])
     p.add_argument("--repeats", type=int, default=1,
-                   help="--section mfma: timed repeats per op and dtype")
+                   help="--section mfma/varlen: timed repeats per op and dtype")
     args = p.parse_args()
     assert torch.cuda.is_available()
     if args.section == "mfma":
         bench_mfma(args.phase, args.dtype, args.repeats)
+        return
+    if args.section == "varlen":
+        bench_varlen(args.dtype, args.repeats)
         return
     dev = torch.device("cuda:0")
     torch.manual_seed(0)

@@ -193,11 +193,22 @@ class BertAttention(nn.Module):
         self.output = BertSelfOutput(config)
         self.dropout_prob = config.attention_probs_dropout_prob
 
-    def forward(self, x: torch.Tensor, seqlens: torch.Tensor) -> torch.Tensor:
+    def forward(
+        self, x: torch.Tensor, seqlens: torch.Tensor, max_seqlen: int = 0
+    ) -> torch.Tensor:
+        """Padded: x [B,S,H] with per-sequence lengths ``seqlens`` [B].
+        Unpadded (``max_seqlen`` > 0): x [T_pad,H] packed, and
+        ``seqlens`` carries cu_seqlens [B+1]."""
         qkv = self.self(x)
-        ctx = ops.fused_attention(
-            qkv, seqlens, self.num_heads, self.dropout_prob, self.training
-        )
+        if max_seqlen:
+            ctx = ops.fused_attention_varlen(
+                qkv, seqlens, max_seqlen, self.num_heads,
+                self.dropout_prob, self.training,
+            )
+        else:
+            ctx = ops.fused_attention(
+                qkv, seqlens, self.num_heads, self.dropout_prob, self.training
+            )
         return self.output(ctx, x)
 
 
@@ -236,8 +247,10 @@ class BertLayer(nn.Module):
         self.output = BertOutput(config)
         self._ffn_gelu = config.hidden_act in ("gelu", "bias_gelu")
 
-    def forward(self, x: torch.Tensor, seqlens: torch.Tensor) -> torch.Tensor:
-        attn = self.attention(x, seqlens)
+    def forward(
+        self, x: torch.Tensor, seqlens: torch.Tensor, max_seqlen: int = 0
+    ) -> torch.Tensor:
+        attn = self.attention(x, seqlens, max_seqlen)
         if self._ffn_gelu and ops.ffn_supported(attn):
             # GELU folded into the FFN GEMM epilogues (ops/ffn.py);
             # FFN2's bias stays fused in the bdrl kernel below
@@ -268,14 +281,14 @@ class BertEncoder(nn.Module):
         self.output_all_encoded_layers = config.output_all_encoded_layers
         self._checkpoint_activations = False
 
-    def _checkpointed_forward(self, x, seqlens):
+    def _checkpointed_forward(self, x, seqlens, max_seqlen=0):
         num_layers = len(self.layer)
         chunk = int(math.sqrt(num_layers)) or 1
 
         def run(start, end):
             def custom(hidden, lens):
                 for layer in self.layer[start:end]:
-                    hidden = layer(hidden, lens)
+                    hidden = layer(hidden, lens, max_seqlen)
                 return hidden
 
             return custom
@@ -287,13 +300,18 @@ class BertEncoder(nn.Module):
             )
         return x
 
-    def forward(self, x: torch.Tensor, seqlens: torch.Tensor):
+    def forward(
+        self, x: torch.Tensor, seqlens: torch.Tensor, max_seqlen: int = 0
+    ):
+        """``max_seqlen`` > 0 selects the unpadded layout: x is the
+        packed [T_pad,H] matrix and ``seqlens`` is cu_seqlens [B+1]
+        (see BertAttention.forward)."""
         all_layers = []
         if self._checkpoint_activations:
-            x = self._checkpointed_forward(x, seqlens)
+            x = self._checkpointed_forward(x, seqlens, max_seqlen)
         else:
             for layer in self.layer:
-                x = layer(x, seqlens)
+                x = layer(x, seqlens, max_seqlen)
                 if self.output_all_encoded_layers:
                     all_layers.append(x)
         if not self.output_all_encoded_layers or self._checkpoint_activations:
@@ -409,6 +427,23 @@ class BertPreTrainedModel(nn.Module):
             if isinstance(module, BertEncoder):
                 module._checkpoint_activations = flag
 
+    def unpad_inputs(self, flag: bool) -> None:
+        """Run the encoder on the valid tokens only (off by default).
+
+        With the flag on, ``BertModel.forward`` packs the embeddings of
+        the positions where ``attention_mask`` is set into one
+        [T_pad, H] matrix, runs every layer on that, and unpacks each
+        returned layer back to [B, S, H]. Differences from the padded
+        path a caller can see: hidden states at padded positions are
+        ZERO (the padded path leaves attention over the valid keys
+        there), a mask that is not a prefix keeps its positions (the
+        padded path reduces it to a length), and each forward reads one
+        integer, the token count, back from the device.
+        """
+        for module in self.modules():
+            if isinstance(module, BertModel):
+                module._unpad_inputs = bool(flag)
+
     @classmethod
     def from_pretrained(
         cls,
@@ -461,6 +496,7 @@ class BertModel(BertPreTrainedModel):
         self.encoder = BertEncoder(config)
         self.pooler = BertPooler(config) if config.next_sentence else None
         self.output_all_encoded_layers = config.output_all_encoded_layers
+        self._unpad_inputs = False
         self.apply_init()
 
     def forward(
@@ -476,12 +512,29 @@ class BertModel(BertPreTrainedModel):
         seqlens = attention_mask.sum(dim=-1, dtype=torch.int32)
 
         emb = self.embeddings(input_ids, token_type_ids)
-        encoded_layers = self.encoder(emb, seqlens)
+        if self._unpad_inputs:
+            encoded_layers = self._unpadded_encoder(emb, attention_mask)
+        else:
+            encoded_layers = self.encoder(emb, seqlens)
         sequence_output = encoded_layers[-1]
         pooled = self.pooler(sequence_output) if self.pooler is not None else None
         if not self.output_all_encoded_layers:
             encoded_layers = encoded_layers[-1]
         return encoded_layers, pooled
+
+
+    def _unpadded_encoder(self, emb: torch.Tensor, attention_mask: torch.Tensor):
+        """Encoder over the packed valid tokens (see ``unpad_inputs``):
+        [B,S,H] embeddings -> list of [B,S,H] layers, zero where the
+        mask is 0."""
+        bsz, seq, hidden = emb.shape
+        dest, cu_seqlens, _total, t_pad = ops.unpad_index(attention_mask)
+        packed = ops.pack_rows(emb.reshape(bsz * seq, hidden), dest, t_pad)
+        layers = self.encoder(packed, cu_seqlens, seq)
+        return [
+            ops.unpack_rows(y, dest, bsz * seq).view(bsz, seq, hidden)
+            for y in layers
+        ]
 
 
 class BertForPreTraining(BertPreTrainedModel):

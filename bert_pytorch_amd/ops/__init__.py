@@ -67,6 +67,12 @@ from .bias_act import fused_bias_gelu  # noqa: E402,F401
 from .fused_residual import fused_bias_dropout_residual_ln  # noqa: E402,F401
 from .embedding import fused_embedding_ln_dropout  # noqa: E402,F401
 from .attention import fused_attention  # noqa: E402,F401
+from .varlen import (  # noqa: E402,F401
+    fused_attention_varlen,
+    pack_rows,
+    unpack_rows,
+    unpad_index,
+)
 from .cross_entropy import fused_cross_entropy  # noqa: E402,F401
 from .linear import fused_linear  # noqa: E402,F401
 from .matmul import linear_nobias  # noqa: E402,F401

@@ -103,6 +103,55 @@ def attention(
     return ctx.transpose(1, 2).reshape(bsz, seq, hidden)
 
 
+def attention_varlen(
+    qkv: torch.Tensor,
+    cu_seqlens: torch.Tensor,
+    max_seqlen: int,
+    num_heads: int,
+    p: float,
+    training: bool,
+) -> torch.Tensor:
+    """Attention over a packed batch.
+
+    qkv: [T_pad, 3*H]; sequence b owns rows cu_seqlens[b]..cu_seqlens[b+1]-1
+    (cu_seqlens: [B+1] int, exclusive prefix sum of the lengths, each at
+    most ``max_seqlen``). Returns [T_pad, H]; rows past cu_seqlens[-1]
+    belong to no sequence and come back as zeros. Each sequence attends
+    to itself only, which is what ``attention`` computes for the valid
+    rows of the padded layout. Eager composite: one ``attention`` call
+    per sequence (the bounds are read on the host).
+    """
+    hidden = qkv.shape[-1] // 3
+    out = qkv.new_zeros(qkv.shape[0], hidden)
+    bounds = [int(v) for v in cu_seqlens.tolist()]
+    for start, end in zip(bounds[:-1], bounds[1:]):
+        n = end - start
+        if n <= 0:
+            continue
+        assert n <= max_seqlen, f"sequence of {n} rows > max_seqlen {max_seqlen}"
+        lens = torch.full((1,), n, dtype=torch.int32, device=qkv.device)
+        out[start:end] = attention(
+            qkv[start:end].unsqueeze(0), lens, num_heads, p, training
+        )[0]
+    return out
+
+
+def pack_rows(x: torch.Tensor, dest: torch.Tensor, t_pad: int) -> torch.Tensor:
+    """[N, H] -> [t_pad, H]: row i goes to row dest[i]; rows with
+    dest[i] < 0 are dropped and rows no dest names are zero."""
+    keep = dest >= 0
+    out = x.new_zeros(t_pad, x.shape[-1])
+    return out.index_copy(0, dest[keep].long(), x[keep])
+
+
+def unpack_rows(y: torch.Tensor, dest: torch.Tensor, rows: int) -> torch.Tensor:
+    """[t_pad, H] -> [rows, H]: inverse of ``pack_rows``; positions with
+    dest[i] < 0 are zero."""
+    keep = dest >= 0
+    gathered = y.index_select(0, dest.clamp(min=0).long())
+    return torch.where(keep.unsqueeze(-1), gathered, torch.zeros_like(gathered))
+
+
 def cross_entropy(
     logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -1
 ) -> torch.Tensor:

@@ -60,6 +60,18 @@ torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
                             torch::Tensor lse, torch::Tensor dmask,
                             int64_t num_heads, double p, int64_t seed,
                             int64_t offset);
+std::vector<torch::Tensor> attention_varlen_fwd(
+    torch::Tensor qkv, torch::Tensor cu_seqlens, int64_t max_seqlen,
+    int64_t num_heads, double p, int64_t seed, int64_t offset);
+torch::Tensor attention_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
+                                   torch::Tensor cu_seqlens,
+                                   int64_t max_seqlen, torch::Tensor out,
+                                   torch::Tensor lse, torch::Tensor dmask,
+                                   int64_t num_heads, double p,
+                                   int64_t seed, int64_t offset);
+torch::Tensor pack_rows(torch::Tensor x, torch::Tensor dest, int64_t t_pad);
+torch::Tensor unpack_rows(torch::Tensor y, torch::Tensor dest,
+                          int64_t padded_rows);
 torch::Tensor multi_tensor_l2norm_sq(std::vector<torch::Tensor> tensors);
 void multi_tensor_clip_scale(std::vector<torch::Tensor> grads,
                              torch::Tensor gnorm_sq, double max_norm);
@@ -110,6 +122,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &bpa::ce_bwd);
   m.def("attention_fwd", &bpa::attention_fwd);
   m.def("attention_bwd", &bpa::attention_bwd);
+  m.def("attention_varlen_fwd", &bpa::attention_varlen_fwd,
+        "packed [T_pad,3H] attention over a cu_seqlens index");
+  m.def("attention_varlen_bwd", &bpa::attention_varlen_bwd);
+  m.def("pack_rows", &bpa::pack_rows,
+        "[B*S,H] -> [T_pad,H]: row i to row dest[i], dest<0 dropped");
+  m.def("unpack_rows", &bpa::unpack_rows,
+        "[T_pad,H] -> [B*S,H]: inverse of pack_rows, dropped rows zero");
   m.def("tr16_probe", &bpa::tr16_probe);
   m.def("wgrad_tn", &bpa::wgrad_tn, py::arg("dy"), py::arg("x"),
         py::arg("splitk_override") = 0);

@@ -32,6 +32,14 @@
 //   pushed ~1k fp32 atomicAdds per wave per q-iter into an fp32
 //   workspace plus a pack kernel; that was the backward bottleneck).
 //
+// Variable-length (packed) layout: the three MFMA kernels take a
+// `bool VARLEN` template parameter. With it the batch is one
+// [T_pad, 3H] matrix of back-to-back sequences addressed through
+// cu_seqlens[B+1]; each sequence's own length bounds its loads, stores
+// and tile loops, so padded rows are neither computed nor read (see
+// seq_row0/seq_rows below and the attention_varlen_* host wrappers).
+// VARLEN=false is the padded layout described above, unchanged.
+//
 // Fragment convention (consistent A/B slot mapping):
 //   A[i][k]/B[k][j]: i|j = lane&15, k = (lane>>4)*4 + (e&3) + 16*(e>>2)
 //   C/D[i][j]:       j = lane&15,   i = (lane>>4)*4 + reg
@@ -150,10 +158,34 @@ static inline std::pair<uint32_t, float> quantize_drop_p(double p) {
   return {t, static_cast<float>(t) / 256.0f};
 }
 
+// Variable-length (packed) addressing. The MFMA kernels below take a
+// `bool VARLEN` template parameter: false is the padded [B, S] layout,
+// where `seqlens[b]` only masks keys and every sequence owns S rows
+// starting at row b*S; true is the packed [T_pad] layout, where the
+// same pointer argument carries cu_seqlens[B+1] - sequence b owns rows
+// cu_seqlens[b] .. cu_seqlens[b+1]-1 and that length replaces S in
+// every load/store guard, the query-row clamp and both tile loops. S
+// (= max_seqlen) keeps addressing lse, delta and the dropout bit-mask,
+// whose layouts do not change. The length is clamped to S so a bad
+// index can not push an lse/delta/mask access past its [.., S] row.
+template <bool VARLEN>
+__device__ __forceinline__ int64_t seq_row0(const int* __restrict__ seqlens,
+                                            int b, int S) {
+  if constexpr (VARLEN) return static_cast<int64_t>(seqlens[b]);
+  return static_cast<int64_t>(b) * S;
+}
+
+template <bool VARLEN>
+__device__ __forceinline__ int seq_rows(const int* __restrict__ seqlens,
+                                        int b, int S) {
+  if constexpr (VARLEN) return min(seqlens[b + 1] - seqlens[b], S);
+  return S;
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
-template <typename T, bool TRAIN_DROP>
+template <typename T, bool TRAIN_DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const T* __restrict__ qkv, const int* __restrict__ seqlens,
     T* __restrict__ out, float* __restrict__ lse_out,
@@ -173,14 +205,19 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   const int g = (lane >> 4), li = lane & 15;
   const int H = NH * 64;
   const int rs3 = 3 * H;  // qkv row stride
-  const T* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
+  const int64_t row0 = seq_row0<VARLEN>(seqlens, b, S);
+  const int L = seq_rows<VARLEN>(seqlens, b, S);  // row bound of this sequence
+  const T* qbase = qkv + row0 * rs3 + h * 64;
   const T* kbase = qbase + H;
   const T* vbase = qbase + 2 * H;
-  const int slen = seqlens[b];
+  const int slen = VARLEN ? L : seqlens[b];
   const float inv_keep = TRAIN_DROP ? 1.f / (1.f - p) : 1.f;
   const int Sw = (S + 31) >> 5;  // mask row stride in words
   const uint32_t* mask_base =
       TRAIN_DROP ? dmask + static_cast<int64_t>(bh) * S * Sw : nullptr;
+
+  // packed layout: a q-tile at or past this sequence's end has no rows
+  if (VARLEN && q0 >= L) return;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* K_lds = reinterpret_cast<T*>(smem);             // [64][72]
@@ -198,7 +235,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 #pragma unroll
   for (int sub = 0; sub < 2; ++sub) {
     q_row[sub] = q0 + wave * 32 + sub * 16 + li;
-    const int q_ld = min(q_row[sub], S - 1);
+    const int q_ld = min(q_row[sub], L - 1);
 #pragma unroll
     for (int c = 0; c < 2; ++c)
       qfrag[sub][c] =
@@ -208,7 +245,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   float m_run[2] = {-1e30f, -1e30f}, l_run[2] = {0.f, 0.f};
   f32x4 acc_o[2][4] = {};
 
-  const int n_kv = (S + 63) / 64;
+  const int n_kv = (L + 63) / 64;
   for (int kt = 0; kt < n_kv; ++kt) {
     const int k0 = kt * 64;
     __syncthreads();
@@ -216,7 +253,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     {
       const int row = tid >> 2, colc = (tid & 3) * 16;
       const int krow = k0 + row;
-      if (krow < S) {
+      if (krow < L) {
         const uint4* src =
             reinterpret_cast<const uint4*>(kbase + static_cast<int64_t>(krow) * rs3 + colc);
         *reinterpret_cast<uint4*>(&K_lds[row * kStride + colc]) = src[0];
@@ -236,7 +273,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
         const int qrow_m = q0 + (tid >> 1);
         const int kw = (k0 >> 5) + (tid & 1);  // 2 words cover 64 keys
         uint32_t bits = 0xFFFFFFFFu;
-        if (qrow_m < S && kw < Sw)
+        if (qrow_m < L && kw < Sw)
           bits = mask_base[static_cast<int64_t>(qrow_m) * Sw + kw];
         mk_lds[tid] = bits;
       }
@@ -270,7 +307,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + t * 16 + g * 4 + r;
-          const bool valid = key < slen && key < S;
+          const bool valid = key < slen && key < L;
           sv[sub][t][r] = valid ? s_acc[sub][t][r] * scale : -1e30f;
           tmax = fmaxf(tmax, sv[sub][t][r]);
         }
@@ -365,15 +402,15 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qr = q0 + wave * 32 + sub * 16 + g * 4 + r;
-        if (qr < S) {
+        if (qr < L) {
           const float l = stat_lds[(wave * 2 + sub) * 16 + g * 4 + r];
           const float o = acc_o[sub][n][r] / (l > 0.f ? l : 1.f);
-          out[(static_cast<int64_t>(b) * S + qr) * H + h * 64 + n * 16 + li] =
+          out[(row0 + qr) * H + h * 64 + n * 16 + li] =
               Tr::from_f32(o);
         }
       }
     }
-    if (g == 0 && q_row[sub] < S)
+    if (g == 0 && q_row[sub] < L)
       lse_out[static_cast<int64_t>(bh) * S + q_row[sub]] =
           m_run[sub] + __logf(l_run[sub] > 0.f ? l_run[sub] : 1.f);
   }
@@ -419,13 +456,52 @@ __global__ void attn_delta_kernel(const T* __restrict__ dout,
   if (part == 0) delta[row] = acc;
 }
 
+// Packed-layout delta: the same lane mapping and the same [B*NH, S]
+// delta rows, with the dO/O row found through cu_seqlens. Slots past a
+// sequence's length have no dO/O row; they are skipped (the 8 lanes of
+// a row leave together) and never read by the backward kernels. A
+// kernel of its own so that the padded kernel above stays byte-for-byte
+// what it was.
+template <typename T>
+__global__ void attn_delta_varlen_kernel(const T* __restrict__ dout,
+                                         const T* __restrict__ out,
+                                         float* __restrict__ delta,
+                                         const int* __restrict__ cu_seqlens,
+                                         int B, int S, int NH) {
+  const int H = NH * 64;
+  const int64_t rows = static_cast<int64_t>(B) * NH * S;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int sub = lane >> 3;
+  const int part = lane & 7;
+  const int64_t row =
+      (static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + wave) * 8 + sub;
+  if (row >= rows) return;
+  const int64_t bh = row / S;
+  const int q = static_cast<int>(row % S);
+  const int b = static_cast<int>(bh) / NH, h = static_cast<int>(bh) % NH;
+  if (q >= seq_rows<true>(cu_seqlens, b, S)) return;
+  const int64_t base =
+      (seq_row0<true>(cu_seqlens, b, S) + q) * H + h * 64 + part * 8;
+  using Tr = Mfma16<T>;
+  T dv[8], ov[8];
+  *reinterpret_cast<uint4*>(dv) = *reinterpret_cast<const uint4*>(dout + base);
+  *reinterpret_cast<uint4*>(ov) = *reinterpret_cast<const uint4*>(out + base);
+  float acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) acc += Tr::to_f32(dv[k]) * Tr::to_f32(ov[k]);
+#pragma unroll
+  for (int off = 4; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE_SIZE);
+  if (part == 0) delta[row] = acc;
+}
+
 // dQ kernel: wave-owns-q structure copied from attn_fwd_kernel.
 // Per K/V tile: recompute S^T = K.Q^T and dP^T = V.dO^T via MFMA,
 // P = exp(S*scale - lse), dS^T = P*(dP - delta)*scale, then chain dS^T
 // lane registers into A-fragments for dQ += dS.K against K^T in LDS
 // (exactly how the forward chains P into the PV product). dQ stays in
 // registers until the single epilogue store into dqkv's Q slots.
-template <typename T, bool TRAIN_DROP>
+template <typename T, bool TRAIN_DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ qkv,
     const int* __restrict__ seqlens, const float* __restrict__ lse,
@@ -445,15 +521,19 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
   const int g = (lane >> 4), li = lane & 15;
   const int H = NH * 64;
   const int rs3 = 3 * H;
-  const T* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
+  const int64_t row0 = seq_row0<VARLEN>(seqlens, b, S);
+  const int L = seq_rows<VARLEN>(seqlens, b, S);  // row bound of this sequence
+  const T* qbase = qkv + row0 * rs3 + h * 64;
   const T* kbase = qbase + H;
   const T* vbase = qbase + 2 * H;
-  const T* dobase = dout + static_cast<int64_t>(b) * S * H + h * 64;
-  const int slen = seqlens[b];
+  const T* dobase = dout + row0 * H + h * 64;
+  const int slen = VARLEN ? L : seqlens[b];
   const float inv_keep = TRAIN_DROP ? 1.f / (1.f - p) : 1.f;
   const int Sw = (S + 31) >> 5;  // mask row stride in words
   const uint32_t* mask_base =
       TRAIN_DROP ? dmask + static_cast<int64_t>(bh) * S * Sw : nullptr;
+
+  if (VARLEN && q0 >= L) return;  // tile past this sequence's end
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // K natural at kTrStride: serves BOTH the S^T-recompute row fragments
@@ -470,7 +550,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
 #pragma unroll
   for (int sub = 0; sub < 2; ++sub) {
     q_row[sub] = q0 + wave * 32 + sub * 16 + li;
-    const int q_ld = min(q_row[sub], S - 1);
+    const int q_ld = min(q_row[sub], L - 1);
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
       qfrag[sub][c] =
@@ -479,21 +559,21 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
           frag_row(dobase + static_cast<int64_t>(q_ld) * H, 32 * c, g);
     }
     lse_q[sub] =
-        (q_row[sub] < S) ? lse[static_cast<int64_t>(bh) * S + q_row[sub]] : 0.f;
+        (q_row[sub] < L) ? lse[static_cast<int64_t>(bh) * S + q_row[sub]] : 0.f;
     dlt_q[sub] =
-        (q_row[sub] < S) ? delta[static_cast<int64_t>(bh) * S + q_row[sub]] : 0.f;
+        (q_row[sub] < L) ? delta[static_cast<int64_t>(bh) * S + q_row[sub]] : 0.f;
   }
 
   f32x4 acc_dq[2][4] = {};
 
-  const int n_kv = (S + 63) / 64;
+  const int n_kv = (L + 63) / 64;
   for (int kt = 0; kt < n_kv; ++kt) {
     const int k0 = kt * 64;
     __syncthreads();
     {
       const int row = tid >> 2, colc = (tid & 3) * 16;
       const int krow = k0 + row;
-      if (krow < S) {
+      if (krow < L) {
         const uint4* ks = reinterpret_cast<const uint4*>(
             kbase + static_cast<int64_t>(krow) * rs3 + colc);
         *reinterpret_cast<uint4*>(&K_lds[row * kTrStride + colc]) = ks[0];
@@ -513,7 +593,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
         const int qrow_m = q0 + (tid >> 1);
         const int kw = (k0 >> 5) + (tid & 1);
         uint32_t bits = 0xFFFFFFFFu;
-        if (qrow_m < S && kw < Sw)
+        if (qrow_m < L && kw < Sw)
           bits = mask_base[static_cast<int64_t>(qrow_m) * Sw + kw];
         mk_lds[tid] = bits;
       }
@@ -562,7 +642,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + t * 16 + g * 4 + r;
-          const bool valid = key < slen && key < S && q_row[sub] < S;
+          const bool valid = key < slen && key < L && q_row[sub] < L;
           const float pr =
               valid ? __expf(sacc[sub][r] * scale - lse_q[sub]) : 0.f;
           float dpd = dpacc[sub][r];
@@ -595,8 +675,8 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int qr = q0 + wave * 32 + sub * 16 + g * 4 + r;
-        if (qr < S) {
-          dqkv[(static_cast<int64_t>(b) * S + qr) * rs3 + h * 64 + n * 16 +
+        if (qr < L) {
+          dqkv[(row0 + qr) * rs3 + h * 64 + n * 16 +
                li] = Tr::from_f32(acc_dq[sub][n][r]);
         }
       }
@@ -604,7 +684,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
   }
 }
 
-template <typename T, bool TRAIN_DROP>
+template <typename T, bool TRAIN_DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(
     const T* __restrict__ dout, const T* __restrict__ qkv,
     const int* __restrict__ seqlens, const float* __restrict__ lse,
@@ -624,15 +704,19 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   const int g = (lane >> 4), li = lane & 15;
   const int H = NH * 64;
   const int rs3 = 3 * H;
-  const T* qbase = qkv + static_cast<int64_t>(b) * S * rs3 + h * 64;
+  const int64_t row0 = seq_row0<VARLEN>(seqlens, b, S);
+  const int L = seq_rows<VARLEN>(seqlens, b, S);  // row bound of this sequence
+  const T* qbase = qkv + row0 * rs3 + h * 64;
   const T* kbase = qbase + H;
   const T* vbase = qbase + 2 * H;
-  const T* dobase = dout + static_cast<int64_t>(b) * S * H + h * 64;
-  const int slen = seqlens[b];
+  const T* dobase = dout + row0 * H + h * 64;
+  const int slen = VARLEN ? L : seqlens[b];
   const float inv_keep = TRAIN_DROP ? 1.f / (1.f - p) : 1.f;
   const int Sw = (S + 31) >> 5;  // mask row stride in words
   const uint32_t* mask_base =
       TRAIN_DROP ? dmask + static_cast<int64_t>(bh) * S * Sw : nullptr;
+
+  if (VARLEN && k0 >= L) return;  // key tile past this sequence's end
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // Q and dO at kTrStride serve BOTH row fragments (S/dP recompute;
@@ -656,7 +740,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     const int row = pass * 64 + (tid >> 2), colc = (tid & 3) * 16;
     const int krow = k0 + row;
     T kv[16], vv[16];
-    if (krow < S) {
+    if (krow < L) {
       const uint4* ks =
           reinterpret_cast<const uint4*>(kbase + static_cast<int64_t>(krow) * rs3 + colc);
       *reinterpret_cast<uint4*>(&kv[0]) = ks[0];
@@ -692,7 +776,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   uint4 pf_q0, pf_q1, pf_d0, pf_d1;
   auto issue_loads = [&](int q0t) {
     const int qrow = q0t + st_row;
-    if (qrow < S) {
+    if (qrow < L) {
       const uint4* qs = reinterpret_cast<const uint4*>(
           qbase + static_cast<int64_t>(qrow) * rs3 + st_colc);
       pf_q0 = qs[0];
@@ -707,7 +791,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   };
   issue_loads(0);
 
-  const int n_q = (S + 63) / 64;
+  const int n_q = (L + 63) / 64;
   for (int qt = 0; qt < n_q; ++qt) {
     const int q0 = qt * 64;
     __syncthreads();  // all waves done reading the previous tile's Q/dO
@@ -722,8 +806,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
           pf_d1;
       if (tid < 64) {
         const int qr = q0 + tid;
-        lse_lds[tid] = (qr < S) ? lse[static_cast<int64_t>(bh) * S + qr] : 0.f;
-        dlt_lds[tid] = (qr < S) ? delta[static_cast<int64_t>(bh) * S + qr] : 0.f;
+        lse_lds[tid] = (qr < L) ? lse[static_cast<int64_t>(bh) * S + qr] : 0.f;
+        dlt_lds[tid] = (qr < L) ? delta[static_cast<int64_t>(bh) * S + qr] : 0.f;
       }
       if (TRAIN_DROP) {
         // keep-mask tile [64 q][128 keys] bits, transposed [word][row]
@@ -733,7 +817,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
         const int kw = (k0 >> 5) + (tid & 3);  // k0 is a multiple of 128
         const int qrow_m = q0 + st_row;
         uint32_t bits = 0xFFFFFFFFu;
-        if (qrow_m < S && kw < Sw)
+        if (qrow_m < L && kw < Sw)
           bits = mask_base[static_cast<int64_t>(qrow_m) * Sw + kw];
         mk_lds[(tid & 3) * 64 + st_row] = bits;
       }
@@ -779,13 +863,13 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
         const int key_abs = k0 + (sub ? key_local1 : key_local0);
-        const bool kvalid = key_abs < slen && key_abs < S;
+        const bool kvalid = key_abs < slen && key_abs < L;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int q_abs = q0 + mq * 16 + g * 4 + r;
           const float row_lse = lse_lds[mq * 16 + g * 4 + r];
           const float d_row = dlt_lds[mq * 16 + g * 4 + r];
-          float pr = (kvalid && q_abs < S)
+          float pr = (kvalid && q_abs < L)
                          ? __expf(acc[sub][r] * scale - row_lse)
                          : 0.f;
           float dpd = dp[sub][r];
@@ -832,8 +916,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
       for (int r = 0; r < 4; ++r) {
         const int dh = m * 16 + g * 4 + r;  // C row = dh/d index
         const int key_abs = k0 + wave * 32 + sub * 16 + li;
-        if (key_abs < S) {
-          const int64_t rowb = static_cast<int64_t>(b) * S + key_abs;
+        if (key_abs < L) {
+          const int64_t rowb = row0 + key_abs;
           dqkv[rowb * rs3 + H + h * 64 + dh] = Tr::from_f32(dk_acc[sub][m][r]);
           dqkv[rowb * rs3 + 2 * H + h * 64 + dh] = Tr::from_f32(dv_acc[sub][m][r]);
         }
@@ -1043,6 +1127,252 @@ torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
                                      num_heads, p, seed, offset);
   return attention_bwd_t<__bf16>(dout, qkv, seqlens, out, lse, dmask,
                                  num_heads, p, seed, offset);
+}
+
+// ---------------------------------------------------------------------------
+// variable-length (packed) host wrappers
+// ---------------------------------------------------------------------------
+// qkv is the packed [T_pad, 3H] QKV GEMM output of a batch whose valid
+// tokens sit back to back; cu_seqlens[B+1] int32 (device) is the
+// exclusive prefix sum of the B lengths, so T = cu_seqlens[B] <= T_pad
+// and every length is <= max_seqlen. Neither is checked here (that
+// would be a device-to-host read); ops/varlen.py builds both from one
+// mask. lse and the keep-mask keep the padded kernel's layout with
+// S := max_seqlen, so dropout_mask_kernel is reused unchanged and the
+// mask equals the padded call's for the same (seed, offset, B, NH, S).
+// Rows [T, T_pad) belong to no sequence: no attention block reads or
+// writes them, and zero_tail_rows_kernel sets them to zero in out /
+// dqkv (every row below T is written by exactly one attention block,
+// so a memset of the whole tensor would only add traffic). lse slots
+// past a sequence's length are left unwritten.
+
+// Zero rows [cu_seqlens[B], t_pad) of a [t_pad, chunks_per_row] matrix
+// of 16-byte chunks. T is only known on the device, so the grid is a
+// fixed size and strides over the tail (under 128 rows when T_pad comes
+// from ops/varlen.py; any size is handled).
+__global__ void zero_tail_rows_kernel(uint4* __restrict__ x,
+                                      const int* __restrict__ cu_seqlens,
+                                      int B, int64_t t_pad,
+                                      int chunks_per_row) {
+  const int64_t first = max(cu_seqlens[B], 0);
+  const int64_t begin = first * chunks_per_row;
+  const int64_t end = t_pad * chunks_per_row;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = begin + static_cast<int64_t>(blockIdx.x) * blockDim.x +
+                   threadIdx.x;
+       i < end; i += stride)
+    x[i] = uint4{0, 0, 0, 0};
+}
+
+static void zero_tail_rows(torch::Tensor& x, const torch::Tensor& cu_seqlens,
+                           hipStream_t stream) {
+  // rows are 128 (out) or 384 (dqkv) bytes per head: whole 16 B chunks
+  const int cpr = static_cast<int>(x.size(1) * x.element_size() / 16);
+  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3(128), dim3(256), 0, stream,
+                     reinterpret_cast<uint4*>(x.data_ptr()),
+                     cu_seqlens.data_ptr<int>(),
+                     static_cast<int>(cu_seqlens.size(0)) - 1, x.size(0),
+                     cpr);
+}
+
+static void check_varlen_args(const torch::Tensor& qkv,
+                              const torch::Tensor& cu_seqlens,
+                              int64_t max_seqlen, int64_t num_heads,
+                              const char* who) {
+  TORCH_CHECK(qkv.dim() == 2 && qkv.is_contiguous(), who,
+              ": qkv must be a contiguous [T_pad, 3H] matrix");
+  TORCH_CHECK(qkv.size(1) == 3 * num_heads * 64, who,
+              ": head_dim must be 64");
+  TORCH_CHECK(cu_seqlens.dim() == 1 && cu_seqlens.size(0) >= 1 &&
+                  cu_seqlens.scalar_type() == torch::kInt32 &&
+                  cu_seqlens.is_contiguous() &&
+                  cu_seqlens.device() == qkv.device(),
+              who, ": cu_seqlens must be a contiguous int32 [B+1] tensor "
+                   "on qkv's device");
+  TORCH_CHECK(max_seqlen >= 1, who, ": max_seqlen must be positive");
+  TORCH_CHECK((cu_seqlens.size(0) - 1) * num_heads <= 65535, who,
+              ": B * num_heads exceeds the grid's y limit");
+}
+
+template <typename T>
+static std::vector<torch::Tensor> attention_varlen_fwd_t(
+    torch::Tensor qkv, torch::Tensor cu_seqlens, int64_t max_seqlen,
+    int64_t num_heads, double p, int64_t seed, int64_t offset) {
+  const int64_t T_pad = qkv.size(0);
+  const int B = static_cast<int>(cu_seqlens.size(0)) - 1;
+  const int S = static_cast<int>(max_seqlen);
+  const int NH = static_cast<int>(num_heads);
+  const int H = NH * 64;
+  auto out = torch::empty({T_pad, H}, qkv.options());
+  auto lse = torch::empty({static_cast<int64_t>(B) * NH, S},
+                          qkv.options().dtype(torch::kFloat32));
+  const bool train_drop = p > 0.0;
+  const int Sw = (S + 31) / 32;
+  auto dmask = train_drop
+                   ? torch::empty({static_cast<int64_t>(B) * NH, S, Sw},
+                                  qkv.options().dtype(torch::kInt32))
+                   : torch::empty({0}, qkv.options().dtype(torch::kInt32));
+  auto stream = at::hip::getCurrentHIPStream();
+  if (T_pad > 0) zero_tail_rows(out, cu_seqlens, stream);
+  if (B == 0) return {out, lse, dmask};
+  const float scale = 1.0f / sqrtf(64.f);
+  dim3 grid((S + 127) / 128, B * NH), block(256);
+  const size_t lds = (64 * kStride + 64 * kTrStride) * sizeof(T) +
+                     4 * 64 * sizeof(float) + 128 * 2 * sizeof(uint32_t);
+  if (train_drop) {
+    const auto [thresh, p_q] = quantize_drop_p(p);
+    const int64_t words = static_cast<int64_t>(B) * NH * S * Sw;
+    hipLaunchKernelGGL(dropout_mask_kernel,
+                       dim3((words + 255) / 256), dim3(256), 0, stream,
+                       reinterpret_cast<uint32_t*>(dmask.data_ptr<int>()),
+                       words, thresh, static_cast<uint64_t>(seed),
+                       static_cast<uint64_t>(offset));
+    hipLaunchKernelGGL((attn_fwd_kernel<T, true, true>), grid, block, lds,
+                       stream, reinterpret_cast<const T*>(qkv.data_ptr()),
+                       cu_seqlens.data_ptr<int>(),
+                       reinterpret_cast<T*>(out.data_ptr()),
+                       lse.data_ptr<float>(),
+                       reinterpret_cast<const uint32_t*>(
+                           dmask.data_ptr<int>()),
+                       B, S, NH, p_q, scale,
+                       static_cast<uint64_t>(seed),
+                       static_cast<uint64_t>(offset));
+  } else {
+    hipLaunchKernelGGL((attn_fwd_kernel<T, false, true>), grid, block, lds,
+                       stream, reinterpret_cast<const T*>(qkv.data_ptr()),
+                       cu_seqlens.data_ptr<int>(),
+                       reinterpret_cast<T*>(out.data_ptr()),
+                       lse.data_ptr<float>(), nullptr, B, S, NH,
+                       static_cast<float>(p), scale,
+                       static_cast<uint64_t>(seed),
+                       static_cast<uint64_t>(offset));
+  }
+  return {out, lse, dmask};
+}
+
+// qkv [T_pad,3H] bf16 or fp16, cu_seqlens [B+1] int32 ->
+// {out [T_pad,H], lse fp32 [B*NH,max_seqlen], keep-mask}
+std::vector<torch::Tensor> attention_varlen_fwd(
+    torch::Tensor qkv, torch::Tensor cu_seqlens, int64_t max_seqlen,
+    int64_t num_heads, double p, int64_t seed, int64_t offset) {
+  const auto dt = qkv.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
+              "attn_varlen_fwd: qkv must be bf16 or fp16, got ", dt);
+  check_varlen_args(qkv, cu_seqlens, max_seqlen, num_heads,
+                    "attn_varlen_fwd");
+  if (dt == torch::kHalf)
+    return attention_varlen_fwd_t<_Float16>(qkv, cu_seqlens, max_seqlen,
+                                            num_heads, p, seed, offset);
+  return attention_varlen_fwd_t<__bf16>(qkv, cu_seqlens, max_seqlen,
+                                        num_heads, p, seed, offset);
+}
+
+template <typename T>
+static torch::Tensor attention_varlen_bwd_t(
+    torch::Tensor dout, torch::Tensor qkv, torch::Tensor cu_seqlens,
+    int64_t max_seqlen, torch::Tensor out, torch::Tensor lse,
+    torch::Tensor dmask, int64_t num_heads, double p, int64_t seed,
+    int64_t offset) {
+  const int B = static_cast<int>(cu_seqlens.size(0)) - 1;
+  const int S = static_cast<int>(max_seqlen);
+  const int NH = static_cast<int>(num_heads);
+  auto dqkv = torch::empty_like(qkv);
+  auto stream = at::hip::getCurrentHIPStream();
+  if (qkv.size(0) > 0) zero_tail_rows(dqkv, cu_seqlens, stream);
+  if (B == 0) return dqkv;
+  auto fopts = qkv.options().dtype(torch::kFloat32);
+  const int64_t rows = static_cast<int64_t>(B) * NH * S;
+  auto delta = torch::empty({rows}, fopts);
+
+  const int64_t delta_waves = (rows + 7) / 8;  // 8 rows per wave
+  hipLaunchKernelGGL(attn_delta_varlen_kernel<T>,
+                     dim3((delta_waves + 3) / 4), dim3(256), 0, stream,
+                     reinterpret_cast<const T*>(dout.data_ptr()),
+                     reinterpret_cast<const T*>(out.data_ptr()),
+                     delta.data_ptr<float>(), cu_seqlens.data_ptr<int>(),
+                     B, S, NH);
+
+  dim3 grid((S + 127) / 128, B * NH), block(256);
+  const size_t lds = (4 * 64 * kStride + 2 * 64 * kTrStride) *
+                         sizeof(T) +
+                     2 * 64 * sizeof(float) + 64 * 4 * sizeof(uint32_t);
+  const size_t lds_dq = (64 * kStride + 64 * kTrStride) * sizeof(T) +
+                        128 * 2 * sizeof(uint32_t);
+  HIP_CHECK(hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&attn_bwd_kernel<T, true, true>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  HIP_CHECK(hipFuncSetAttribute(
+      reinterpret_cast<const void*>(&attn_bwd_kernel<T, false, true>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  const float scale = 1.0f / sqrtf(64.f);
+  const bool train_drop = p > 0.0;
+  const float p_q = quantize_drop_p(p).second;
+  const uint32_t* mask_ptr =
+      train_drop ? reinterpret_cast<const uint32_t*>(dmask.data_ptr<int>())
+                 : nullptr;
+  auto args = [&](auto kernel, size_t lds_bytes) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream,
+                       reinterpret_cast<const T*>(dout.data_ptr()),
+                       reinterpret_cast<const T*>(qkv.data_ptr()),
+                       cu_seqlens.data_ptr<int>(), lse.data_ptr<float>(),
+                       delta.data_ptr<float>(), mask_ptr,
+                       reinterpret_cast<T*>(dqkv.data_ptr()), B, S, NH,
+                       p_q, scale,
+                       static_cast<uint64_t>(seed),
+                       static_cast<uint64_t>(offset));
+  };
+  if (train_drop) {
+    args(attn_bwd_kernel<T, true, true>, lds);
+    args(attn_dq_kernel<T, true, true>, lds_dq);
+  } else {
+    args(attn_bwd_kernel<T, false, true>, lds);
+    args(attn_dq_kernel<T, false, true>, lds_dq);
+  }
+  return dqkv;
+}
+
+// Packed backward -> dqkv [T_pad,3H]. All operands are checked for
+// dtype, shape and contiguity before any launch.
+torch::Tensor attention_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
+                                   torch::Tensor cu_seqlens,
+                                   int64_t max_seqlen, torch::Tensor out,
+                                   torch::Tensor lse, torch::Tensor dmask,
+                                   int64_t num_heads, double p,
+                                   int64_t seed, int64_t offset) {
+  const auto dt = qkv.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
+              "attn_varlen_bwd: qkv must be bf16 or fp16, got ", dt);
+  check_varlen_args(qkv, cu_seqlens, max_seqlen, num_heads,
+                    "attn_varlen_bwd");
+  TORCH_CHECK(dout.scalar_type() == dt,
+              "attn_varlen_bwd: dout dtype ", dout.scalar_type(),
+              " does not match qkv dtype ", dt);
+  TORCH_CHECK(out.scalar_type() == dt, "attn_varlen_bwd: out dtype ",
+              out.scalar_type(), " does not match qkv dtype ", dt);
+  const int64_t T_pad = qkv.size(0), H = qkv.size(1) / 3;
+  const int64_t bnh = (cu_seqlens.size(0) - 1) * num_heads;
+  TORCH_CHECK(dout.dim() == 2 && dout.size(0) == T_pad &&
+                  dout.size(1) == H && out.sizes() == dout.sizes(),
+              "attn_varlen_bwd: dout and out must be [T_pad, H]");
+  TORCH_CHECK(out.is_contiguous(), "attn_varlen_bwd: out not contiguous");
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
+                  lse.numel() == bnh * max_seqlen,
+              "attn_varlen_bwd: lse must be fp32 [B*NH, max_seqlen]");
+  if (p > 0.0)
+    TORCH_CHECK(dmask.scalar_type() == torch::kInt32 &&
+                    dmask.is_contiguous() &&
+                    dmask.numel() ==
+                        bnh * max_seqlen * ((max_seqlen + 31) / 32),
+                "attn_varlen_bwd: keep-mask does not match "
+                "[B*NH, max_seqlen, ceil(max_seqlen/32)]");
+  auto dout_c = dout.contiguous();
+  if (dt == torch::kHalf)
+    return attention_varlen_bwd_t<_Float16>(dout_c, qkv, cu_seqlens,
+                                            max_seqlen, out, lse, dmask,
+                                            num_heads, p, seed, offset);
+  return attention_varlen_bwd_t<__bf16>(dout_c, qkv, cu_seqlens, max_seqlen,
+                                        out, lse, dmask, num_heads, p, seed,
+                                        offset);
 }
 
 }  // namespace bpa

@@ -48,11 +48,17 @@ def parse_args(argv=None):
     parser.add_argument("--seed", type=int, default=42)
     parser.add_argument("--fp16", action="store_true")
     parser.add_argument("--bf16", action="store_true")
+    parser.add_argument("--unpad", action="store_true",
+                        help="run the encoder on the valid tokens only "
+                             "(packed rows + variable-length attention); "
+                             "off by default")
     parser.add_argument("--do_train", action="store_true")
     parser.add_argument("--do_eval", action="store_true")
     parser.add_argument("--local_rank", type=int,
                         default=int(os.environ.get("LOCAL_RANK", 0)))
-    return merge_config_and_args(parser, argv)
+    ns = merge_config_and_args(parser, argv)
+    ns.unpad = bool(ns.unpad)  # may come from the JSON config
+    return ns
 
 
 def compute_metrics(preds, labels, num_labels):
@@ -89,6 +95,22 @@ def evaluate(model, loader, device, mixed, num_labels):
     return compute_metrics(preds, labels, num_labels)
 
 
+def prepare_model(args, config, num_labels, device):
+    """Build the tagger, load --init_checkpoint, apply model toggles."""
+    model = BertForTokenClassification(config, num_labels=num_labels)
+    if args.init_checkpoint:
+        state = torch.load(args.init_checkpoint, map_location="cpu",
+                           weights_only=False)
+        if isinstance(state, dict) and "model" in state:
+            state = state["model"]
+        state = {k.removeprefix("module."): v for k, v in state.items()}
+        model.load_state_dict(state, strict=False)
+    model.to(device)
+    if args.unpad:
+        model.unpad_inputs(True)
+    return model
+
+
 def main(args=None):
     if args is None:
         args = parse_args()
@@ -123,15 +145,7 @@ def main(args=None):
         args.max_seq_length, labels=train_set.labels,
         pad_label_id=PAD_LABEL_ID,
     )
-    model = BertForTokenClassification(config, num_labels=train_set.num_labels)
-    if args.init_checkpoint:
-        state = torch.load(args.init_checkpoint, map_location="cpu",
-                           weights_only=False)
-        if isinstance(state, dict) and "model" in state:
-            state = state["model"]
-        state = {k.removeprefix("module."): v for k, v in state.items()}
-        model.load_state_dict(state, strict=False)
-    model.to(device)
+    model = prepare_model(args, config, train_set.num_labels, device)
     mixed = args.bf16 or args.fp16
 
     train_loader = DataLoader(train_set, batch_size=args.batch_size,

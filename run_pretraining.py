@@ -86,6 +86,10 @@ def parse_arguments(args=None) -> argparse.Namespace:
                         help="bf16 autocast (MI355X-preferred; wins over --fp16)")
     parser.add_argument("--num_steps_per_checkpoint", type=int, default=200)
     parser.add_argument("--checkpoint_activations", action="store_true")
+    parser.add_argument("--unpad", action="store_true",
+                        help="run the encoder on the valid tokens only "
+                             "(packed rows + variable-length attention); "
+                             "off by default, not available with --kfac")
     parser.add_argument("--vocab_file", type=str, default=None)
     parser.add_argument("--mask_token_index", type=int, default=None)
     parser.add_argument("--vocab_pad_multiple", type=int, default=64,
@@ -111,8 +115,14 @@ def parse_arguments(args=None) -> argparse.Namespace:
     ns = merge_config_and_args(parser, args)
     # bool-ish JSON values
     for key in ("fp16", "bf16", "bf16_weights", "kfac", "disable_progress_bar",
-                "checkpoint_activations"):
+                "checkpoint_activations", "unpad"):
         setattr(ns, key, bool(getattr(ns, key)))
+    if ns.unpad and ns.kfac:
+        raise ValueError(
+            "--unpad cannot be combined with --kfac: the K-FAC factor hooks "
+            "would see the packed batch's zero tail rows, and K-FAC on the "
+            "unpadded encoder is not supported. Drop one of the two flags."
+        )
     return ns
 
 
@@ -190,6 +200,8 @@ def prepare_model(args, device):
                 prm.data = prm.data.to(torch.bfloat16)
     if args.checkpoint_activations:
         model.checkpoint_activations(True)
+    if args.unpad:
+        model.unpad_inputs(True)
     global_steps = max(0, resume_step - args.previous_phase_end_step)
     model = comm.wrap_ddp(model, args.local_rank,
                           grad_compress=args.grad_compress)

@@ -68,13 +68,19 @@ def parse_args(argv=None):
     parser.add_argument("--fp16", action="store_true",
                         help="mixed precision (bf16 autocast on MI355X)")
     parser.add_argument("--bf16", action="store_true")
+    parser.add_argument("--unpad", action="store_true",
+                        help="run the encoder on the valid tokens only "
+                             "(packed rows + variable-length attention); "
+                             "off by default")
     parser.add_argument("--do_lower_case", action="store_true", default=True)
     parser.add_argument("--version_2_with_negative", action="store_true")
     parser.add_argument("--null_score_diff_threshold", type=float, default=0.0)
     parser.add_argument("--max_grad_norm", type=float, default=1.0)
     parser.add_argument("--local_rank", type=int,
                         default=int(os.environ.get("LOCAL_RANK", 0)))
-    return merge_config_and_args(parser, argv)
+    ns = merge_config_and_args(parser, argv)
+    ns.unpad = bool(ns.unpad)  # may come from the JSON config
+    return ns
 
 
 def cached_features(args, examples, tokenizer, is_training, split):
@@ -111,6 +117,25 @@ def features_to_dataset(features, is_training):
     )
 
 
+def prepare_model(args, config, device, log=None):
+    """Build the QA model, load --init_checkpoint, apply model toggles."""
+    model = BertForQuestionAnswering(config)
+    if args.init_checkpoint:
+        state = torch.load(args.init_checkpoint, map_location="cpu",
+                           weights_only=False)
+        if isinstance(state, dict) and "model" in state:
+            state = state["model"]
+        state = {k.removeprefix("module."): v for k, v in state.items()}
+        missing, unexpected = model.load_state_dict(state, strict=False)
+        if log is not None:
+            log.info("loaded init checkpoint (missing=%d unexpected=%d)",
+                     len(missing), len(unexpected))
+    model.to(device)
+    if args.unpad:
+        model.unpad_inputs(True)
+    return model
+
+
 def main(args=None):
     if args is None:
         args = parse_args()
@@ -138,17 +163,7 @@ def main(args=None):
         vocab_file, lowercase=getattr(config, "lowercase", args.do_lower_case)
     )
 
-    model = BertForQuestionAnswering(config)
-    if args.init_checkpoint:
-        state = torch.load(args.init_checkpoint, map_location="cpu",
-                           weights_only=False)
-        if isinstance(state, dict) and "model" in state:
-            state = state["model"]
-        state = {k.removeprefix("module."): v for k, v in state.items()}
-        missing, unexpected = model.load_state_dict(state, strict=False)
-        log.info("loaded init checkpoint (missing=%d unexpected=%d)",
-                 len(missing), len(unexpected))
-    model.to(device)
+    model = prepare_model(args, config, device, log)
 
     mixed = args.bf16 or args.fp16
     autocast_dtype = torch.bfloat16  # MI355X-preferred

@@ -22,6 +22,7 @@ sources = [
     "csrc/ops/embedding.hip",
     "csrc/ops/cross_entropy.hip",
     "csrc/ops/attention.hip",
+    "csrc/ops/varlen.hip",
     "csrc/ops/wgrad.hip",
     "csrc/ops/mlm_head.hip",
     "csrc/ops/gemm_epilogue.cpp",
