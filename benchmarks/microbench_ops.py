@@ -320,6 +320,22 @@ def main():
     us = timeit(lambda: ext.ln_bwd(dyt, x, w, mean2, rstd2))
     report("ln_bwd[rows,1024]", us, 3 * rows * H * e)
 
+    # ---- embedding gather + add + LayerNorm + dropout forward (fp32
+    # tables and a 16-bit output, as under autocast)
+    ids = torch.randint(0, V, (b, s), device=dev)
+    tt = torch.randint(0, 2, (b, s), device=dev)
+    word = torch.randn(V, H, device=dev)
+    pos = torch.randn(512, H, device=dev)
+    tok = torch.randn(2, H, device=dev)
+    us = timeit(
+        lambda: ext.embedding_ln_dropout_fwd(ids, tt, word, pos, tok, w, bt,
+                                             0.1, 1e-12, 123, 0, dt)
+    )
+    # three fp32 table rows read per output row (nominal: repeated ids and
+    # the 128 position rows come from cache, so the rate can exceed the
+    # copy ceiling); fp32 z, y and the byte mask written
+    report("embed_fwd[rows,1024]", us, rows * H * (3 * 4 + 4 + e + 1))
+
     # ---- attention fwd/bwd
     qkv = torch.randn(b, s, 3 * H, device=dev, dtype=dt)
     seqlens = torch.full((b,), s, device=dev, dtype=torch.int32)

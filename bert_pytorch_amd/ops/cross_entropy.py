@@ -3,7 +3,9 @@
 Replaces ``nn.CrossEntropyLoss(ignore_index=-1)`` over the MLM vocab
 (reference: run_pretraining.py:58-72) with one kernel that never
 materializes the [N, V] log-softmax: forward stores only the per-row
-logsumexp; backward recomputes softmax on the fly.
+logsumexp; backward recomputes softmax on the fly. A vocabulary that is
+no multiple of the 16-byte slice (8 elements in bf16/fp16, 4 in fp32)
+runs the kernels' scalar instantiation: correct, slower; pad it for speed.
 Kernel source: csrc/ops/cross_entropy.hip.
 """
 

@@ -1,9 +1,12 @@
 """Fused LayerNorm (HIP, gfx950).
 
 Replaces Apex ``FusedLayerNormAffineFunction`` (reference:
-src/modeling.py:299-335). Forward: one wave-per-row Welford-free two-pass
-reduction in registers/DPP; backward: fused dx + two-stage partial
-reduction for dgamma/dbeta. Kernel source: csrc/ops/layernorm.hip.
+src/modeling.py:299-335). Forward: one block per row, the row held in
+registers; the mean and then the variance as the mean of (x - mean)^2 are
+two block reductions over those registers (two-pass: no sumsq - mean^2
+cancellation on rows whose mean is large against their spread).
+Backward: block-per-row dx + two-stage partial reduction for
+dgamma/dbeta. Kernel source: csrc/ops/layernorm.hip.
 """
 
 from __future__ import annotations

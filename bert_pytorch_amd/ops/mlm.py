@@ -82,7 +82,13 @@ class _MlmDecoderLoss(torch.autograd.Function):
         # so they contribute nothing to dw/dbias and slice away from dh
         dh = (dlogits @ w)[: ctx.rows]
         dw = dlogits.transpose(0, 1) @ h
-        dbias = ext.col_sum(dlogits)
+        if dlogits.shape[1] % 8 == 0:
+            dbias = ext.col_sum(dlogits)
+        else:
+            # an unpadded vocabulary (30522): rows are not 16 B aligned, so
+            # ce_bwd ran its scalar instantiation and col_sum's 16 B
+            # slices do not apply; a plain fp32 column sum instead
+            dbias = dlogits.sum(0, dtype=torch.float32)
         return dh, dw, dbias, None, None
 
 

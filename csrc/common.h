@@ -99,6 +99,23 @@ __device__ __forceinline__ void block_reduce_sum2(float& a, float& b,
   }
 }
 
+// cross-wave sum of one value (blockDim.x/64 waves, size known only at
+// run time); result broadcast to all threads. smem must hold
+// blockDim.x/64 floats and, like block_reduce_sum2, is single-use: a
+// kernel that reduces twice passes two buffers.
+__device__ __forceinline__ float block_reduce_sum1(float a, float* smem) {
+  const int lane = threadIdx.x & (WAVE_SIZE - 1);
+  const int wave = threadIdx.x / WAVE_SIZE;
+  const int nwaves = blockDim.x / WAVE_SIZE;
+  a = wave_reduce_sum(a);
+  if (nwaves == 1) return a;
+  if (lane == 0) smem[wave] = a;
+  __syncthreads();
+  a = 0.f;
+  for (int w = 0; w < nwaves; ++w) a += smem[w];
+  return a;
+}
+
 // reduce across a block of NW waves through LDS; result broadcast to all.
 template <int NW>
 __device__ __forceinline__ float block_reduce_sum(float v, float* smem) {

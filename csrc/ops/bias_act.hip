@@ -16,6 +16,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "../checks.h"
 #include "../common.h"
 
 namespace bpa {
@@ -179,8 +180,11 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor bias) {
 
 std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor bias) {
+  check_rows_2d("bias_gelu_bwd", "x", x);
+  check_like("bias_gelu_bwd", "dy", dy, "x", x);
   const int64_t rows = x.size(0);
   const int H = x.size(1);
+  check_param("bias_gelu_bwd", "bias", bias, H);
   auto bias_f = bias.contiguous().to(torch::kFloat32);
   auto dx = torch::empty_like(x);
   auto fopts = x.options().dtype(torch::kFloat32);
@@ -190,7 +194,6 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   const int stripe_count =
       static_cast<int>((rows + rows_per_block - 1) / rows_per_block);
   torch::Tensor dbias;
-  auto dy_c = dy.contiguous();
   DISPATCH_FLOATING2(x.scalar_type(), "bias_gelu_bwd", [&] {
     TORCH_CHECK(H % kVec == 0, "bias_gelu_bwd: H % ", kVec, " != 0");
     auto part = torch::empty({stripe_count, H}, fopts);
@@ -199,7 +202,7 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
     const size_t lds = NW * WAVE_SIZE * kVec * sizeof(float);
     hipLaunchKernelGGL((bias_gelu_bwd_kernel<scalar_t, kVec, NW>), grid,
                        dim3(NW * WAVE_SIZE), lds, stream,
-                       reinterpret_cast<const scalar_t*>(dy_c.data_ptr()),
+                       reinterpret_cast<const scalar_t*>(dy.data_ptr()),
                        reinterpret_cast<const scalar_t*>(x.data_ptr()),
                        bias_f.data_ptr<float>(),
                        reinterpret_cast<scalar_t*>(dx.data_ptr()),

@@ -5,10 +5,16 @@
 // [N, V] log-softmax: one 256-thread block per row does an online
 // max/sum-exp reduction and stores only the per-row logsumexp.
 // Backward recomputes softmax on the fly.
+//
+// Rows are read and written as 16 B slices (VEC = 8 or 4), which needs
+// V % VEC == 0 for every row to start 16 B aligned. Any other V (the
+// unpadded 30522-word BERT vocabulary) runs the VEC = 1 instantiation of
+// the same kernels: scalar accesses, same arithmetic.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "../checks.h"
 #include "../common.h"
 
 namespace bpa {
@@ -27,7 +33,10 @@ __global__ void ce_fwd_kernel(const T* __restrict__ logits,
   float m = -INFINITY, s = 0.f;
   for (int c = threadIdx.x * VEC; c < V; c += blockDim.x * VEC) {
     T v[VEC];
-    *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(xr + c);
+    if constexpr (VEC == 1)
+      v[0] = xr[c];
+    else
+      *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(xr + c);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       float f = DTraits<T>::to_f32(v[k]);
@@ -110,14 +119,20 @@ __global__ void ce_bwd_kernel(const float* __restrict__ dloss,
   const float row_lse = lse[row];
   for (int c = threadIdx.x * VEC; c < V; c += blockDim.x * VEC) {
     T v[VEC], o[VEC];
-    *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(xr + c);
+    if constexpr (VEC == 1)
+      v[0] = xr[c];
+    else
+      *reinterpret_cast<uint4*>(v) = *reinterpret_cast<const uint4*>(xr + c);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       float p = __expf(DTraits<T>::to_f32(v[k]) - row_lse);
       float g = scale * (p - ((c + k) == label ? 1.f : 0.f));
       o[k] = DTraits<T>::from_f32(g);
     }
-    *reinterpret_cast<uint4*>(dr + c) = *reinterpret_cast<const uint4*>(o);
+    if constexpr (VEC == 1)
+      dr[c] = o[0];
+    else
+      *reinterpret_cast<uint4*>(dr + c) = *reinterpret_cast<const uint4*>(o);
   }
 }
 
@@ -152,13 +167,18 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels,
   auto lse = torch::empty({rows}, fopts);
   auto stream = at::hip::getCurrentHIPStream();
   DISPATCH_CE(logits.scalar_type(), "ce_fwd", [&] {
-    TORCH_CHECK(V % kVec == 0, "ce_fwd: V % ", kVec, " != 0");
-    hipLaunchKernelGGL((ce_fwd_kernel<scalar_t, kVec>), dim3(rows), dim3(256),
-                       0, stream,
-                       reinterpret_cast<const scalar_t*>(logits.data_ptr()),
-                       labels_c.data_ptr<int64_t>(),
-                       row_loss.data_ptr<float>(),
-                       lse.data_ptr<float>(), rows, V, ignore_index);
+    auto launch = [&](auto vec_c) {
+      hipLaunchKernelGGL(
+          (ce_fwd_kernel<scalar_t, decltype(vec_c)::value>), dim3(rows),
+          dim3(256), 0, stream,
+          reinterpret_cast<const scalar_t*>(logits.data_ptr()),
+          labels_c.data_ptr<int64_t>(), row_loss.data_ptr<float>(),
+          lse.data_ptr<float>(), rows, V, ignore_index);
+    };
+    if (V % kVec == 0)
+      launch(std::integral_constant<int, kVec>{});
+    else
+      launch(std::integral_constant<int, 1>{});
   });
   hipLaunchKernelGGL(ce_reduce_kernel, dim3(1), dim3(256), 0, stream,
                      row_loss.data_ptr<float>(), sums.data_ptr<float>(),
@@ -169,21 +189,36 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels,
 torch::Tensor ce_bwd(torch::Tensor dloss, torch::Tensor logits,
                      torch::Tensor labels, torch::Tensor lse,
                      torch::Tensor count, int64_t ignore_index) {
+  check_rows_2d("ce_bwd", "logits", logits);
   const int64_t rows = logits.size(0);
   const int V = logits.size(1);
+  check_row_stat("ce_bwd", "lse", lse, rows);
+  TORCH_CHECK(labels.numel() == rows, "ce_bwd: labels must have ", rows,
+              " elements, got ", labels.sizes());
+  TORCH_CHECK(dloss.numel() == 1 && count.numel() == 1,
+              "ce_bwd: dloss and count must be scalars");
   auto labels_c = labels.contiguous();
   auto dlogits = torch::empty_like(logits);
   auto dloss_f = dloss.to(torch::kFloat32).reshape({1}).contiguous();
   auto count_i = count.to(torch::kInt32).reshape({1}).contiguous();
   auto stream = at::hip::getCurrentHIPStream();
   DISPATCH_CE(logits.scalar_type(), "ce_bwd", [&] {
-    hipLaunchKernelGGL((ce_bwd_kernel<scalar_t, kVec>), dim3(rows), dim3(256),
-                       0, stream, dloss_f.data_ptr<float>(),
-                       reinterpret_cast<const scalar_t*>(logits.data_ptr()),
-                       labels_c.data_ptr<int64_t>(), lse.data_ptr<float>(),
-                       count_i.data_ptr<int>(),
-                       reinterpret_cast<scalar_t*>(dlogits.data_ptr()), rows,
-                       V, ignore_index);
+    auto launch = [&](auto vec_c) {
+      hipLaunchKernelGGL(
+          (ce_bwd_kernel<scalar_t, decltype(vec_c)::value>), dim3(rows),
+          dim3(256), 0, stream, dloss_f.data_ptr<float>(),
+          reinterpret_cast<const scalar_t*>(logits.data_ptr()),
+          labels_c.data_ptr<int64_t>(), lse.data_ptr<float>(),
+          count_i.data_ptr<int>(),
+          reinterpret_cast<scalar_t*>(dlogits.data_ptr()), rows, V,
+          ignore_index);
+    };
+    // same rule as ce_fwd: a row of an unaligned V starts off a 16 B
+    // boundary and its last slice would run into the next row
+    if (V % kVec == 0)
+      launch(std::integral_constant<int, kVec>{});
+    else
+      launch(std::integral_constant<int, 1>{});
   });
   return dlogits;
 }

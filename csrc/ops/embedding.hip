@@ -13,6 +13,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "../checks.h"
 #include "../common.h"
 
 namespace bpa {
@@ -30,7 +31,7 @@ __global__ void embed_fwd_kernel(
     uint64_t seed, uint64_t offset) {
   // one BLOCK per row; ITEMS elements per thread held in registers
   // through the mean/var reduction (see layernorm.hip ln_fwd_kernel)
-  __shared__ float red[32];
+  __shared__ float red[16], red2[16];
   const int row = blockIdx.x;
   if (row >= rows) return;
   const int64_t base = static_cast<int64_t>(row) * H;
@@ -46,7 +47,7 @@ __global__ void embed_fwd_kernel(
   constexpr int ITEMS = 2;  // covers H <= 2*blockDim*VEC
   float zv[ITEMS][VEC];
   int cols[ITEMS];
-  float sum = 0.f, sumsq = 0.f;
+  float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
     const int c = (i * blockDim.x + threadIdx.x) * VEC;
@@ -59,7 +60,6 @@ __global__ void embed_fwd_kernel(
         if (HAS_TOK) t += DTraits<TW>::to_f32(trow[c + k]);
         zv[i][k] = t;
         sum += t;
-        sumsq += t * t;
       }
       if (sizeof(float) * VEC == 16) {
         *reinterpret_cast<uint4*>(z + base + c) =
@@ -70,9 +70,20 @@ __global__ void embed_fwd_kernel(
       }
     }
   }
-  block_reduce_sum2(sum, sumsq, red);
-  const float mu = sum / H;
-  const float var = fmaxf(sumsq / H - mu * mu, 0.f);
+  // two-pass variance over the register-resident row (layernorm.hip)
+  const float mu = block_reduce_sum1(sum, red) / H;
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    if (cols[i] < H) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const float d = zv[i][k] - mu;
+        sq += d * d;
+      }
+    }
+  }
+  const float var = block_reduce_sum1(sq, red2) / H;
   const float rs = rsqrtf(var + eps);
   if (threadIdx.x == 0) {
     mean[row] = mu;
@@ -416,10 +427,25 @@ std::vector<torch::Tensor> embedding_ln_dropout_bwd(
     int64_t max_pos, int64_t n_types) {
   const int batch = ids.size(0), seq_len = ids.size(1);
   const int rows = batch * seq_len;
+  TORCH_CHECK(z.scalar_type() == torch::kFloat32, "embed_bwd: z dtype ",
+              z.scalar_type(), " must be ", torch::kFloat32);
+  TORCH_CHECK(z.dim() == 2 && z.size(0) == rows && z.is_contiguous(),
+              "embed_bwd: z must be contiguous [", rows, ", H], got ",
+              z.sizes());
   const int H = z.size(1);
+  TORCH_CHECK(dy.numel() == static_cast<int64_t>(rows) * H &&
+                  dy.size(-1) == H && dy.is_contiguous(),
+              "embed_bwd: dy must be contiguous [", batch, ", ", seq_len,
+              ", ", H, "], got ", dy.sizes());
+  check_row_stat("embed_bwd", "mean", mean, rows);
+  check_row_stat("embed_bwd", "rstd", rstd, rows);
+  check_param("embed_bwd", "gamma", gamma, H);
+  if (p > 0.0) check_drop_mask("embed_bwd", mask, rows, H);
+  TORCH_CHECK(seq_len <= max_pos, "embed_bwd: sequence length ", seq_len,
+              " exceeds max_pos ", max_pos);
   auto ids_c = ids.contiguous();
   auto gamma_f = gamma.contiguous().to(torch::kFloat32);
-  auto dy2 = dy.contiguous().view({rows, H});
+  auto dy2 = dy.view({rows, H});
   const bool train_drop = p > 0.0;
   const bool has_tok = tt.has_value() && n_types > 0;
 
@@ -433,6 +459,7 @@ std::vector<torch::Tensor> embedding_ln_dropout_bwd(
   auto stream = at::hip::getCurrentHIPStream();
   const size_t lds = NW * 2 * static_cast<size_t>(H) * sizeof(float);
   DISPATCH_OUT(dy.scalar_type(), "embed_bwd", [&] {
+    TORCH_CHECK(H % kVec == 0, "embed_bwd: H % ", kVec, " != 0");
     auto launch = [&](auto train_c) {
       if (lds > 48 * 1024) {
         HIP_CHECK(hipFuncSetAttribute(

@@ -18,6 +18,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "../checks.h"
 #include "../common.h"
 
 namespace bpa {
@@ -32,7 +33,7 @@ __global__ void bdrl_fwd_kernel(
     uint8_t* __restrict__ mask, float* __restrict__ mean,
     float* __restrict__ rstd, int rows, int H, float p, float eps,
     uint64_t seed, uint64_t offset) {
-  __shared__ float red[32];
+  __shared__ float red[16], red2[16];
   const int row = blockIdx.x;
   if (row >= rows) return;
   const int64_t base = static_cast<int64_t>(row) * H;
@@ -41,7 +42,7 @@ __global__ void bdrl_fwd_kernel(
 
   float zv[ITEMS][VEC];
   int cols[ITEMS];
-  float sum = 0.f, sumsq = 0.f;
+  float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
     const int c = (i * blockDim.x + threadIdx.x) * VEC;
@@ -71,7 +72,6 @@ __global__ void bdrl_fwd_kernel(
         zv[i][k] = t;
         zt[k] = DTraits<T>::from_f32(t);
         sum += t;
-        sumsq += t * t;
       }
       *reinterpret_cast<uint4*>(z + base + c) = *reinterpret_cast<const uint4*>(zt);
       if (TRAIN_DROP) {
@@ -84,9 +84,20 @@ __global__ void bdrl_fwd_kernel(
       }
     }
   }
-  block_reduce_sum2(sum, sumsq, red);
-  const float mu = sum / H;
-  const float var = fmaxf(sumsq / H - mu * mu, 0.f);
+  // two-pass variance over the register-resident row (layernorm.hip)
+  const float mu = block_reduce_sum1(sum, red) / H;
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    if (cols[i] < H) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const float d = zv[i][k] - mu;
+        sq += d * d;
+      }
+    }
+  }
+  const float var = block_reduce_sum1(sq, red2) / H;
   const float rs = rsqrtf(var + eps);
   if (threadIdx.x == 0) {
     mean[row] = mu;
@@ -279,9 +290,14 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
 std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
     torch::Tensor dy, torch::Tensor z, torch::Tensor mask, torch::Tensor gamma,
     torch::Tensor mean, torch::Tensor rstd, double p, bool has_bias) {
+  check_rows_2d("bdrl_bwd", "z", z);
+  check_like("bdrl_bwd", "dy", dy, "z", z);
   const int rows = z.size(0), H = z.size(1);
+  check_row_stat("bdrl_bwd", "mean", mean, rows);
+  check_row_stat("bdrl_bwd", "rstd", rstd, rows);
+  check_param("bdrl_bwd", "gamma", gamma, H);
+  if (p > 0.0) check_drop_mask("bdrl_bwd", mask, rows, H);
   auto gamma_f = gamma.contiguous().to(torch::kFloat32);
-  auto dy_c = dy.contiguous();
   auto dx = torch::empty_like(z);
   auto dz_res = torch::empty_like(z);
   const int rows_per_chunk = 16;  // halves partial-buffer traffic; 16 independent loads/thread
@@ -299,7 +315,7 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
           (bdrl_bwd_dx_kernel<scalar_t, kVec, decltype(items_c)::value,
                               decltype(train_c)::value>),
           dim3(rows), dim3(threads), 0, stream,
-          reinterpret_cast<const scalar_t*>(dy_c.data_ptr()),
+          reinterpret_cast<const scalar_t*>(dy.data_ptr()),
           reinterpret_cast<const scalar_t*>(z.data_ptr()),
           train_drop ? mask.data_ptr<uint8_t>() : nullptr,
           gamma_f.data_ptr<float>(), mean.data_ptr<float>(),
@@ -328,7 +344,7 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
     else
       by_items(std::false_type{});
     launch_col_stats<scalar_t, kVec>(
-        reinterpret_cast<const scalar_t*>(dy_c.data_ptr()),
+        reinterpret_cast<const scalar_t*>(dy.data_ptr()),
         reinterpret_cast<const scalar_t*>(z.data_ptr()),
         reinterpret_cast<const scalar_t*>(dx.data_ptr()),
         mean.data_ptr<float>(), rstd.data_ptr<float>(),

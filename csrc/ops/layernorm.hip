@@ -18,6 +18,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include "../checks.h"
 #include "../common.h"
 
 namespace bpa {
@@ -30,14 +31,14 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
                               T* __restrict__ y, float* __restrict__ mean,
                               float* __restrict__ rstd, int rows, int H,
                               float eps) {
-  __shared__ float red[32];
+  __shared__ float red[16], red2[16];
   const int row = blockIdx.x;
   if (row >= rows) return;
   const int64_t base = static_cast<int64_t>(row) * H;
 
   float v[ITEMS][VEC];
   int cols[ITEMS];
-  float sum = 0.f, sumsq = 0.f;
+  float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
     const int c = (i * blockDim.x + threadIdx.x) * VEC;
@@ -49,13 +50,24 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
       for (int k = 0; k < VEC; ++k) {
         v[i][k] = DTraits<T>::to_f32(t[k]);
         sum += v[i][k];
-        sumsq += v[i][k] * v[i][k];
       }
     }
   }
-  block_reduce_sum2(sum, sumsq, red);
-  const float mu = sum / H;
-  const float var = fmaxf(sumsq / H - mu * mu, 0.f);
+  // two-pass variance over the register-resident row: sumsq/H - mu^2
+  // cancels catastrophically once |mean| >> std
+  const float mu = block_reduce_sum1(sum, red) / H;
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    if (cols[i] < H) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const float d = v[i][k] - mu;
+        sq += d * d;
+      }
+    }
+  }
+  const float var = block_reduce_sum1(sq, red2) / H;
   const float rs = rsqrtf(var + eps);
   if (threadIdx.x == 0) {
     mean[row] = mu;
@@ -402,8 +414,12 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor gamma,
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x,
                                   torch::Tensor gamma, torch::Tensor mean,
                                   torch::Tensor rstd) {
-  TORCH_CHECK(dy.sizes() == x.sizes(), "ln_bwd: shape mismatch");
+  check_rows_2d("ln_bwd", "x", x);
+  check_like("ln_bwd", "dy", dy, "x", x);
   const int rows = x.size(0), H = x.size(1);
+  check_row_stat("ln_bwd", "mean", mean, rows);
+  check_row_stat("ln_bwd", "rstd", rstd, rows);
+  check_param("ln_bwd", "gamma", gamma, H);
   auto gamma_f = gamma.contiguous().to(torch::kFloat32);
   auto dx = torch::empty_like(x);
   const int rows_per_chunk = 16;  // halves partial-buffer traffic; 16 independent loads/thread
@@ -411,21 +427,20 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x,
   auto opts = x.options().dtype(torch::kFloat32);
   auto part = torch::empty({n_chunks, 2 * H}, opts);
   auto stream = at::hip::getCurrentHIPStream();
-  auto dy_c = dy.contiguous();
   DISPATCH_FLOATING(x.scalar_type(), "ln_bwd", [&] {
     TORCH_CHECK(H % kVec == 0, "ln_bwd: H must be a multiple of ", kVec);
     launch_by_items(H / kVec, [&](auto items_c, int threads) {
       hipLaunchKernelGGL(
           (ln_bwd_dx_kernel<scalar_t, kVec, decltype(items_c)::value>),
           dim3(rows), dim3(threads), 0, stream,
-          reinterpret_cast<const scalar_t*>(dy_c.data_ptr()),
+          reinterpret_cast<const scalar_t*>(dy.data_ptr()),
           reinterpret_cast<const scalar_t*>(x.data_ptr()),
           gamma_f.data_ptr<float>(), mean.data_ptr<float>(),
           rstd.data_ptr<float>(),
           reinterpret_cast<scalar_t*>(dx.data_ptr()), rows, H);
     });
     launch_col_stats<scalar_t, kVec>(
-        reinterpret_cast<const scalar_t*>(dy_c.data_ptr()),
+        reinterpret_cast<const scalar_t*>(dy.data_ptr()),
         reinterpret_cast<const scalar_t*>(x.data_ptr()), nullptr,
         mean.data_ptr<float>(), rstd.data_ptr<float>(),
         part.data_ptr<float>(), rows, H, rows_per_chunk, n_chunks, false,
