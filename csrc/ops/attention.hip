@@ -54,6 +54,7 @@
 #include <utility>
 
 #include "../common.h"
+#include "../ops.h"
 #include "../mfma_types.h"
 
 namespace bpa {

@@ -10,18 +10,17 @@
 // Backward fuses the dbias column reduction into the dx pass: each wave
 // keeps a per-lane fp32 accumulator over its row slice (registers, no
 // LDS traffic in the hot loop), waves combine through an 8 KiB LDS slab,
-// blocks write [grid.y, H] partials reduced by col_reduce_kernel. This
+// blocks write [grid.y, H] partials reduced by col_reduce_full. This
 // removes the old second full read of dx (100 MB at phase-1 FFN shapes).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 #include "../checks.h"
-#include "../common.h"
+#include "../ops.h"
+#include "rowwise.h"
 
 namespace bpa {
-
-torch::Tensor col_reduce_full(torch::Tensor parts);  // layernorm.hip
 
 template <typename T, int VEC>
 __global__ void bias_gelu_fwd_kernel(const T* __restrict__ x,
@@ -114,7 +113,7 @@ __global__ void bias_gelu_bwd_kernel(const T* __restrict__ dy,
 
 // Generic column sum [rows, H] -> fp32 [H] (two-stage, deterministic).
 // Used for the packed-QKV bias gradient (replacing ATen's bf16 reduce
-// at ~2.5 TB/s with a streaming partial pass + col_reduce).
+// at ~2.5 TB/s with a streaming partial pass + col_reduce_full).
 template <typename T, int VEC>
 __global__ void col_sum_partial_kernel(const T* __restrict__ x,
                                        float* __restrict__ part, int rows,
@@ -136,25 +135,6 @@ __global__ void col_sum_partial_kernel(const T* __restrict__ x,
   for (int k = 0; k < VEC; ++k) p[k] = acc[k];
 }
 
-#define DISPATCH_FLOATING2(TYPE, NAME, ...)                                  \
-  [&] {                                                                      \
-    if (TYPE == at::kBFloat16) {                                             \
-      using scalar_t = __hip_bfloat16;                                       \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kHalf) {                                          \
-      using scalar_t = __half;                                               \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kFloat) {                                         \
-      using scalar_t = float;                                                \
-      constexpr int kVec = 4;                                                \
-      return __VA_ARGS__();                                                  \
-    } else {                                                                 \
-      TORCH_CHECK(false, NAME, ": unsupported dtype");                       \
-    }                                                                        \
-  }()
-
 torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor bias) {
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), "bias_gelu_fwd: bad x");
   const int64_t rows = x.size(0);
@@ -162,17 +142,15 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor bias) {
   auto bias_f = bias.contiguous().to(torch::kFloat32);
   auto y = torch::empty_like(x);
   auto stream = at::hip::getCurrentHIPStream();
-  DISPATCH_FLOATING2(x.scalar_type(), "bias_gelu_fwd", [&] {
+  DISPATCH_ROW_DTYPE(x.scalar_type(), "bias_gelu_fwd", [&] {
     TORCH_CHECK(H % kVec == 0, "bias_gelu_fwd: H % ", kVec, " != 0");
     const int vec_per_row = H / kVec;
     const int threads = tmin(256, ((vec_per_row + 63) / 64) * 64);
     dim3 grid((vec_per_row + threads - 1) / threads,
               static_cast<unsigned>(tmin<int64_t>(rows, 65535)));
     hipLaunchKernelGGL((bias_gelu_fwd_kernel<scalar_t, kVec>), grid,
-                       dim3(threads), 0, stream,
-                       reinterpret_cast<const scalar_t*>(x.data_ptr()),
-                       bias_f.data_ptr<float>(),
-                       reinterpret_cast<scalar_t*>(y.data_ptr()),
+                       dim3(threads), 0, stream, dptr<scalar_t>(x),
+                       bias_f.data_ptr<float>(), dptr<scalar_t>(y),
                        static_cast<int>(rows), H);
   });
   return y;
@@ -194,20 +172,17 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
   const int stripe_count =
       static_cast<int>((rows + rows_per_block - 1) / rows_per_block);
   torch::Tensor dbias;
-  DISPATCH_FLOATING2(x.scalar_type(), "bias_gelu_bwd", [&] {
+  DISPATCH_ROW_DTYPE(x.scalar_type(), "bias_gelu_bwd", [&] {
     TORCH_CHECK(H % kVec == 0, "bias_gelu_bwd: H % ", kVec, " != 0");
     auto part = torch::empty({stripe_count, H}, fopts);
     const int lanes_per_row = WAVE_SIZE;  // one wave per row slice
     dim3 grid((H / kVec + lanes_per_row - 1) / lanes_per_row, stripe_count);
     const size_t lds = NW * WAVE_SIZE * kVec * sizeof(float);
     hipLaunchKernelGGL((bias_gelu_bwd_kernel<scalar_t, kVec, NW>), grid,
-                       dim3(NW * WAVE_SIZE), lds, stream,
-                       reinterpret_cast<const scalar_t*>(dy.data_ptr()),
-                       reinterpret_cast<const scalar_t*>(x.data_ptr()),
-                       bias_f.data_ptr<float>(),
-                       reinterpret_cast<scalar_t*>(dx.data_ptr()),
-                       part.data_ptr<float>(), static_cast<int>(rows), H,
-                       rows_per_block);
+                       dim3(NW * WAVE_SIZE), lds, stream, dptr<scalar_t>(dy),
+                       dptr<scalar_t>(x), bias_f.data_ptr<float>(),
+                       dptr<scalar_t>(dx), part.data_ptr<float>(),
+                       static_cast<int>(rows), H, rows_per_block);
     dbias = col_reduce_full(part);
   });
   if (bias.scalar_type() != torch::kFloat32) {
@@ -225,15 +200,14 @@ torch::Tensor col_sum(torch::Tensor x) {
   auto fopts = x.options().dtype(torch::kFloat32);
   torch::Tensor out;
   auto stream = at::hip::getCurrentHIPStream();
-  DISPATCH_FLOATING2(x.scalar_type(), "col_sum", [&] {
+  DISPATCH_ROW_DTYPE(x.scalar_type(), "col_sum", [&] {
     TORCH_CHECK(H % kVec == 0, "col_sum: H % ", kVec, " != 0");
     auto part = torch::empty({n_chunks, H}, fopts);
     const int slices = H / kVec;
     const int threads = tmin(256, ((slices + 63) / 64) * 64);
     dim3 grid((slices + threads - 1) / threads, n_chunks);
     hipLaunchKernelGGL((col_sum_partial_kernel<scalar_t, kVec>), grid,
-                       dim3(threads), 0, stream,
-                       reinterpret_cast<const scalar_t*>(x.data_ptr()),
+                       dim3(threads), 0, stream, dptr<scalar_t>(x),
                        part.data_ptr<float>(), rows, H, rows_per_chunk);
     out = col_reduce_full(part);
   });

@@ -15,7 +15,8 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "../checks.h"
-#include "../common.h"
+#include "../ops.h"
+#include "rowwise.h"
 
 namespace bpa {
 
@@ -136,25 +137,6 @@ __global__ void ce_bwd_kernel(const float* __restrict__ dloss,
   }
 }
 
-#define DISPATCH_CE(TYPE, NAME, ...)                                         \
-  [&] {                                                                      \
-    if (TYPE == at::kBFloat16) {                                             \
-      using scalar_t = __hip_bfloat16;                                       \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kHalf) {                                          \
-      using scalar_t = __half;                                               \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kFloat) {                                         \
-      using scalar_t = float;                                                \
-      constexpr int kVec = 4;                                                \
-      return __VA_ARGS__();                                                  \
-    } else {                                                                 \
-      TORCH_CHECK(false, NAME, ": unsupported dtype");                       \
-    }                                                                        \
-  }()
-
 std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels,
                                   int64_t ignore_index) {
   TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "ce_fwd: bad logits");
@@ -166,12 +148,11 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor labels,
   auto sums = torch::empty({2}, fopts);  // {loss_sum, count}
   auto lse = torch::empty({rows}, fopts);
   auto stream = at::hip::getCurrentHIPStream();
-  DISPATCH_CE(logits.scalar_type(), "ce_fwd", [&] {
+  DISPATCH_ROW_DTYPE(logits.scalar_type(), "ce_fwd", [&] {
     auto launch = [&](auto vec_c) {
       hipLaunchKernelGGL(
           (ce_fwd_kernel<scalar_t, decltype(vec_c)::value>), dim3(rows),
-          dim3(256), 0, stream,
-          reinterpret_cast<const scalar_t*>(logits.data_ptr()),
+          dim3(256), 0, stream, dptr<scalar_t>(logits),
           labels_c.data_ptr<int64_t>(), row_loss.data_ptr<float>(),
           lse.data_ptr<float>(), rows, V, ignore_index);
     };
@@ -202,16 +183,14 @@ torch::Tensor ce_bwd(torch::Tensor dloss, torch::Tensor logits,
   auto dloss_f = dloss.to(torch::kFloat32).reshape({1}).contiguous();
   auto count_i = count.to(torch::kInt32).reshape({1}).contiguous();
   auto stream = at::hip::getCurrentHIPStream();
-  DISPATCH_CE(logits.scalar_type(), "ce_bwd", [&] {
+  DISPATCH_ROW_DTYPE(logits.scalar_type(), "ce_bwd", [&] {
     auto launch = [&](auto vec_c) {
       hipLaunchKernelGGL(
           (ce_bwd_kernel<scalar_t, decltype(vec_c)::value>), dim3(rows),
           dim3(256), 0, stream, dloss_f.data_ptr<float>(),
-          reinterpret_cast<const scalar_t*>(logits.data_ptr()),
-          labels_c.data_ptr<int64_t>(), lse.data_ptr<float>(),
-          count_i.data_ptr<int>(),
-          reinterpret_cast<scalar_t*>(dlogits.data_ptr()), rows, V,
-          ignore_index);
+          dptr<scalar_t>(logits), labels_c.data_ptr<int64_t>(),
+          lse.data_ptr<float>(), count_i.data_ptr<int>(),
+          dptr<scalar_t>(dlogits), rows, V, ignore_index);
     };
     // same rule as ce_fwd: a row of an unaligned V starts off a 16 B
     // boundary and its last slice would run into the next row

@@ -14,11 +14,10 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "../checks.h"
-#include "../common.h"
+#include "../ops.h"
+#include "rowwise.h"
 
 namespace bpa {
-
-torch::Tensor col_reduce_full(torch::Tensor parts);  // layernorm.hip
 
 template <typename T, typename TW, int VEC, bool HAS_TOK, bool TRAIN_DROP>
 __global__ void embed_fwd_kernel(
@@ -29,8 +28,9 @@ __global__ void embed_fwd_kernel(
     uint8_t* __restrict__ mask, float* __restrict__ mean,
     float* __restrict__ rstd, int rows, int seq_len, int H, float p, float eps,
     uint64_t seed, uint64_t offset) {
-  // one BLOCK per row; ITEMS elements per thread held in registers
-  // through the mean/var reduction (see layernorm.hip ln_fwd_kernel)
+  // one BLOCK per row; ITEMS slices per thread held in registers
+  // through the mean/var reduction (row core: rowwise.h). Keeps its own
+  // ITEMS and thread count, not launch_by_items.
   __shared__ float red[16], red2[16];
   const int row = blockIdx.x;
   if (row >= rows) return;
@@ -61,71 +61,26 @@ __global__ void embed_fwd_kernel(
         zv[i][k] = t;
         sum += t;
       }
-      if (sizeof(float) * VEC == 16) {
-        *reinterpret_cast<uint4*>(z + base + c) =
-            *reinterpret_cast<const uint4*>(zv[i]);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) z[base + c + k] = zv[i][k];
-      }
+      store_slice(z + base + c, zv[i]);
     }
   }
-  // two-pass variance over the register-resident row (layernorm.hip)
-  const float mu = block_reduce_sum1(sum, red) / H;
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    if (cols[i] < H) {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        const float d = zv[i][k] - mu;
-        sq += d * d;
-      }
-    }
-  }
-  const float var = block_reduce_sum1(sq, red2) / H;
-  const float rs = rsqrtf(var + eps);
-  if (threadIdx.x == 0) {
-    mean[row] = mu;
-    rstd[row] = rs;
-  }
+  const RowStats st =
+      ln_row_stats(zv, cols, sum, H, eps, red, red2, mean, rstd, row);
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
     const int c = cols[i];
     if (c < H) {
       T ov[VEC];
       uint8_t mv[VEC];
-      if (TRAIN_DROP) {
-#pragma unroll
-        for (int q = 0; q < VEC / 4; ++q) {
-          uint32_t r4[4];
-          philox(offset + (base + c) / 4 + q, r4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            mv[q * 4 + j] = u32_to_uniform(r4[j]) >= p ? 1 : 0;
-        }
-      }
+      if (TRAIN_DROP) keep_mask(philox, offset, base + c, p, mv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        float t = (zv[i][k] - mu) * rs * gamma[c + k] + beta[c + k];
+        float t = ln_affine(zv[i][k], st, gamma[c + k], beta[c + k]);
         if (TRAIN_DROP) t = mv[k] ? t * keep_scale : 0.f;
         ov[k] = DTraits<T>::from_f32(t);
       }
-      if (sizeof(T) * VEC == 16) {
-        *reinterpret_cast<uint4*>(y + base + c) =
-            *reinterpret_cast<const uint4*>(ov);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) y[base + c + k] = ov[k];
-      }
-      if (TRAIN_DROP) {
-        if (VEC == 8)
-          *reinterpret_cast<uint2*>(mask + base + c) =
-              *reinterpret_cast<const uint2*>(mv);
-        else
-          *reinterpret_cast<uint32_t*>(mask + base + c) =
-              *reinterpret_cast<const uint32_t*>(mv);
-      }
+      store_slice(y + base + c, ov);
+      if (TRAIN_DROP) store_mask(mask + base + c, mv);
     }
   }
 }
@@ -135,10 +90,10 @@ template <typename T, int VEC, int NW, bool TRAIN_DROP>
 __global__ void embed_bwd_dz_kernel(
     const T* __restrict__ dy, const float* __restrict__ z,
     const uint8_t* __restrict__ mask, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean,
-    const float* __restrict__ rstd, float* __restrict__ dz,
-    float* __restrict__ part_dgamma, float* __restrict__ part_dbeta, int rows,
-    int H, float p, int rows_per_block) {
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    float* __restrict__ dz, float* __restrict__ part_dgamma,
+    float* __restrict__ part_dbeta, int rows, int H, float p,
+    int rows_per_block) {
   const int lane = threadIdx.x & (WAVE_SIZE - 1);
   const int wave = threadIdx.x / WAVE_SIZE;
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -331,25 +286,6 @@ __global__ void embed_bwd_tok_kernel(const float* __restrict__ dz,
   for (int c = threadIdx.x; c < n_types * H; c += blockDim.x) out[c] = lt[c];
 }
 
-#define DISPATCH_OUT(TYPE, NAME, ...)                                        \
-  [&] {                                                                      \
-    if (TYPE == at::kBFloat16) {                                             \
-      using out_t = __hip_bfloat16;                                          \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kHalf) {                                          \
-      using out_t = __half;                                                  \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kFloat) {                                         \
-      using out_t = float;                                                   \
-      constexpr int kVec = 4;                                                \
-      return __VA_ARGS__();                                                  \
-    } else {                                                                 \
-      TORCH_CHECK(false, NAME, ": unsupported dtype");                       \
-    }                                                                        \
-  }()
-
 std::vector<torch::Tensor> embedding_ln_dropout_fwd(
     torch::Tensor ids, c10::optional<torch::Tensor> tt, torch::Tensor word,
     torch::Tensor pos, c10::optional<torch::Tensor> tok, torch::Tensor gamma,
@@ -381,40 +317,33 @@ std::vector<torch::Tensor> embedding_ln_dropout_fwd(
   auto mean = torch::empty({rows}, fopts);
   auto rstd = torch::empty({rows}, fopts);
   auto stream = at::hip::getCurrentHIPStream();
-  DISPATCH_OUT(out_dtype, "embed_fwd", [&] {
-    using scalar_out_t = out_t;
-    constexpr int kVecOuter = kVec;
+  DISPATCH_ROW_DTYPE(out_dtype, "embed_fwd", [&] {
+    using out_t = scalar_t;  // the inner dispatch re-binds scalar_t, kVec
+    constexpr int kVecOut = kVec;
     TORCH_CHECK(H % kVec == 0, "embed_fwd: H % ", kVec, " != 0");
     const int slices = H / kVec;
     const int threads =
         tmin(1024, (((slices + 1) / 2 + WAVE_SIZE - 1) / WAVE_SIZE) *
                        WAVE_SIZE);
     TORCH_CHECK(slices <= 2 * threads, "embed_fwd: H too large");
-    DISPATCH_OUT(word.scalar_type(), "embed_fwd_table", [&] {
-      using tw_t = out_t;  // inner dispatch alias
-      auto launch = [&](auto tok_flag, auto train_c) {
-        hipLaunchKernelGGL(
-            (embed_fwd_kernel<scalar_out_t, tw_t, kVecOuter,
-                              decltype(tok_flag)::value,
-                              decltype(train_c)::value>),
-            dim3(rows), dim3(threads), 0, stream, ids_c.data_ptr<int64_t>(),
-            has_tok ? tt_c.data_ptr<int64_t>() : nullptr,
-            reinterpret_cast<const tw_t*>(word.data_ptr()),
-            reinterpret_cast<const tw_t*>(pos.data_ptr()),
-            has_tok ? reinterpret_cast<const tw_t*>(tok->data_ptr())
-                    : nullptr,
-            gamma_f.data_ptr<float>(), beta_f.data_ptr<float>(),
-            reinterpret_cast<scalar_out_t*>(y.data_ptr()),
-            z.data_ptr<float>(),
-            train_drop ? mask.data_ptr<uint8_t>() : nullptr,
-            mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, seq_len,
-            H, static_cast<float>(p), static_cast<float>(eps),
-            static_cast<uint64_t>(seed), static_cast<uint64_t>(offset));
-      };
-      if (has_tok && train_drop) launch(std::true_type{}, std::true_type{});
-      else if (has_tok) launch(std::true_type{}, std::false_type{});
-      else if (train_drop) launch(std::false_type{}, std::true_type{});
-      else launch(std::false_type{}, std::false_type{});
+    DISPATCH_ROW_DTYPE(word.scalar_type(), "embed_fwd_table", [&] {
+      using tw_t = scalar_t;
+      by_flag(has_tok, [&](auto tok_c) {
+        by_flag(train_drop, [&](auto train_c) {
+          hipLaunchKernelGGL(
+              (embed_fwd_kernel<out_t, tw_t, kVecOut, decltype(tok_c)::value,
+                                decltype(train_c)::value>),
+              dim3(rows), dim3(threads), 0, stream, ids_c.data_ptr<int64_t>(),
+              has_tok ? tt_c.data_ptr<int64_t>() : nullptr, dptr<tw_t>(word),
+              dptr<tw_t>(pos), has_tok ? dptr<tw_t>(*tok) : nullptr,
+              gamma_f.data_ptr<float>(), beta_f.data_ptr<float>(),
+              dptr<out_t>(y), z.data_ptr<float>(),
+              train_drop ? mask.data_ptr<uint8_t>() : nullptr,
+              mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, seq_len,
+              H, static_cast<float>(p), static_cast<float>(eps),
+              static_cast<uint64_t>(seed), static_cast<uint64_t>(offset));
+        });
+      });
     });
   });
   return {y, z, mask, mean, rstd};
@@ -458,28 +387,25 @@ std::vector<torch::Tensor> embedding_ln_dropout_bwd(
   auto part_b = torch::empty({nblocks, H}, fopts);
   auto stream = at::hip::getCurrentHIPStream();
   const size_t lds = NW * 2 * static_cast<size_t>(H) * sizeof(float);
-  DISPATCH_OUT(dy.scalar_type(), "embed_bwd", [&] {
+  DISPATCH_ROW_DTYPE(dy.scalar_type(), "embed_bwd", [&] {
     TORCH_CHECK(H % kVec == 0, "embed_bwd: H % ", kVec, " != 0");
-    auto launch = [&](auto train_c) {
+    by_flag(train_drop, [&](auto train_c) {
+      auto kernel =
+          &embed_bwd_dz_kernel<scalar_t, kVec, NW, decltype(train_c)::value>;
       if (lds > 48 * 1024) {
         HIP_CHECK(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(
-                &embed_bwd_dz_kernel<out_t, kVec, NW,
-                                     decltype(train_c)::value>),
+            reinterpret_cast<const void*>(kernel),
             hipFuncAttributeMaxDynamicSharedMemorySize, lds));
       }
       hipLaunchKernelGGL(
-          (embed_bwd_dz_kernel<out_t, kVec, NW, decltype(train_c)::value>),
-          dim3(nblocks), dim3(NW * WAVE_SIZE), lds, stream,
-          reinterpret_cast<const out_t*>(dy2.data_ptr()), z.data_ptr<float>(),
+          kernel, dim3(nblocks), dim3(NW * WAVE_SIZE), lds, stream,
+          dptr<scalar_t>(dy2), z.data_ptr<float>(),
           train_drop ? mask.data_ptr<uint8_t>() : nullptr,
-          gamma_f.data_ptr<float>(), nullptr, mean.data_ptr<float>(),
+          gamma_f.data_ptr<float>(), mean.data_ptr<float>(),
           rstd.data_ptr<float>(), dz.data_ptr<float>(),
           part_g.data_ptr<float>(), part_b.data_ptr<float>(), rows, H,
           static_cast<float>(p), rows_per_block);
-    };
-    if (train_drop) launch(std::true_type{});
-    else launch(std::false_type{});
+    });
   });
 
   auto d_word = torch::zeros({vocab, H}, fopts);

@@ -24,6 +24,8 @@
 #include <tuple>
 #include <vector>
 
+#include "../ops.h"
+
 namespace bpa {
 
 namespace {

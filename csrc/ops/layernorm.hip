@@ -14,12 +14,17 @@
 //   chunks (per-lane register accumulators, coalesced loads) writes
 //   [n_chunks, 2H] partials folded by col_reduce_full — measured
 //   faster than fusing the column accumulation into the dx grid.
+//
+// The row cores (two-pass mean/rstd, affine, backward sums) are in
+// rowwise.h, shared with fused_residual.hip and embedding.hip; col_stats
+// and col_reduce_full below are declared in ops.h for the other files.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 #include "../checks.h"
-#include "../common.h"
+#include "../ops.h"
+#include "rowwise.h"
 
 namespace bpa {
 
@@ -45,7 +50,7 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
     cols[i] = c;
     if (c < H) {
       T t[VEC];
-      *reinterpret_cast<uint4*>(t) = *reinterpret_cast<const uint4*>(x + base + c);
+      load_slice(x + base + c, t);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         v[i][k] = DTraits<T>::to_f32(t[k]);
@@ -53,39 +58,9 @@ __global__ void ln_fwd_kernel(const T* __restrict__ x,
       }
     }
   }
-  // two-pass variance over the register-resident row: sumsq/H - mu^2
-  // cancels catastrophically once |mean| >> std
-  const float mu = block_reduce_sum1(sum, red) / H;
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    if (cols[i] < H) {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        const float d = v[i][k] - mu;
-        sq += d * d;
-      }
-    }
-  }
-  const float var = block_reduce_sum1(sq, red2) / H;
-  const float rs = rsqrtf(var + eps);
-  if (threadIdx.x == 0) {
-    mean[row] = mu;
-    rstd[row] = rs;
-  }
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int c = cols[i];
-    if (c < H) {
-      T o[VEC];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        o[k] = DTraits<T>::from_f32((v[i][k] - mu) * rs * gamma[c + k] +
-                                    beta[c + k]);
-      }
-      *reinterpret_cast<uint4*>(y + base + c) = *reinterpret_cast<const uint4*>(o);
-    }
-  }
+  const RowStats st =
+      ln_row_stats(v, cols, sum, H, eps, red, red2, mean, rstd, row);
+  ln_affine_store<T, VEC, ITEMS>(v, cols, st, gamma, beta, y + base, H);
 }
 
 // backward dx: one BLOCK per row, the mirror of ln_fwd_kernel — dy/x
@@ -114,20 +89,15 @@ __global__ void ln_bwd_dx_kernel(const T* __restrict__ dy,
     cols[i] = c;
     if (c < H) {
       T dt[VEC], xt[VEC];
-      *reinterpret_cast<uint4*>(dt) = *reinterpret_cast<const uint4*>(dy + base + c);
-      *reinterpret_cast<uint4*>(xt) = *reinterpret_cast<const uint4*>(x + base + c);
+      load_slice(dy + base + c, dt);
+      load_slice(x + base + c, xt);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        xh[i][k] = (DTraits<T>::to_f32(xt[k]) - mu) * rs;
-        dw[i][k] = DTraits<T>::to_f32(dt[k]) * gamma[c + k];
-        s1 += dw[i][k] * xh[i][k];
-        s2 += dw[i][k];
-      }
+      for (int k = 0; k < VEC; ++k)
+        ln_bwd_elem(xt[k], dt[k], &gamma[c + k], mu, rs, dw[i][k], xh[i][k],
+                    s1, s2);
     }
   }
-  block_reduce_sum2(s1, s2, red);
-  s1 /= H;
-  s2 /= H;
+  ln_bwd_row_means(s1, s2, H, red);
 #pragma unroll
   for (int i = 0; i < ITEMS; ++i) {
     const int c = cols[i];
@@ -135,8 +105,9 @@ __global__ void ln_bwd_dx_kernel(const T* __restrict__ dy,
       T o[VEC];
 #pragma unroll
       for (int k = 0; k < VEC; ++k)
-        o[k] = DTraits<T>::from_f32(rs * (dw[i][k] - s2 - xh[i][k] * s1));
-      *reinterpret_cast<uint4*>(dx + base + c) = *reinterpret_cast<const uint4*>(o);
+        o[k] = DTraits<T>::from_f32(
+            ln_bwd_dz(dw[i][k], xh[i][k], rs, s1, s2));
+      store_slice(dx + base + c, o);
     }
   }
 }
@@ -146,7 +117,7 @@ __global__ void ln_bwd_dx_kernel(const T* __restrict__ dy,
 //   (+ dbias[c] += dx_src[r][c] when dx_src != nullptr)
 // Each thread owns VEC contiguous columns and loops its row chunk with
 // independent (software-pipelineable) loads; partials [n_chunks, nsl*H]
-// are folded by col_reduce_kernel. Shared by ln_bwd and bdrl_bwd.
+// are folded by col_reduce_full. Shared by ln_bwd and bdrl_bwd.
 template <typename T, int VEC, bool HAS_BIAS>
 __global__ void col_stats_kernel(const T* __restrict__ dy,
                                  const T* __restrict__ z,
@@ -186,37 +157,6 @@ __global__ void col_stats_kernel(const T* __restrict__ dy,
     if (HAS_BIAS) p[2 * H + k] = acc_bias[k];
   }
 }
-
-// instantiation helper shared with fused_residual.hip
-template <typename T, int VEC>
-void launch_col_stats(const T* dy, const T* z, const T* dx_src,
-                      const float* mean, const float* rstd, float* part,
-                      int rows, int H, int rows_per_chunk, int n_chunks,
-                      bool has_bias, hipStream_t stream) {
-  const int threads = tmin(256, ((H / VEC + 63) / 64) * 64);
-  dim3 grid((H / VEC + threads - 1) / threads, n_chunks);
-  if (has_bias) {
-    hipLaunchKernelGGL((col_stats_kernel<T, VEC, true>), grid, dim3(threads),
-                       0, stream, dy, z, dx_src, mean, rstd, part, rows, H,
-                       rows_per_chunk);
-  } else {
-    hipLaunchKernelGGL((col_stats_kernel<T, VEC, false>), grid, dim3(threads),
-                       0, stream, dy, z, dx_src, mean, rstd, part, rows, H,
-                       rows_per_chunk);
-  }
-}
-
-template void launch_col_stats<__hip_bfloat16, 8>(
-    const __hip_bfloat16*, const __hip_bfloat16*, const __hip_bfloat16*,
-    const float*, const float*, float*, int, int, int, int, bool, hipStream_t);
-template void launch_col_stats<__half, 8>(const __half*, const __half*,
-                                          const __half*, const float*,
-                                          const float*, float*, int, int, int,
-                                          int, bool, hipStream_t);
-template void launch_col_stats<float, 4>(const float*, const float*,
-                                         const float*, const float*,
-                                         const float*, float*, int, int, int,
-                                         int, bool, hipStream_t);
 
 // Deterministic blocked column reduce: out[j][c] = sum over the j-th
 // contiguous row block of parts[p][c]. Each thread owns 4 consecutive
@@ -320,6 +260,11 @@ __global__ void col_reduce_ordered_kernel(const float* __restrict__ parts,
   for (int k = 0; k < nk; ++k) out[c + k] = sum[k];
 }
 
+// partial rows per y-block of col_reduce_ordered_kernel: measured best of
+// 16/32/64/128 (fewer chunk sums shorten the last block's fold, longer
+// chunks cost parallelism in the first phase)
+constexpr int kColChunk = 32;
+
 torch::Tensor col_reduce_full(torch::Tensor parts) {
   const int nparts = parts.size(0);
   const int S = parts.size(1);
@@ -332,10 +277,7 @@ torch::Tensor col_reduce_full(torch::Tensor parts) {
                        S, nparts, out.data_ptr<float>());
     return out;
   }
-  // 32 partial rows per y-block: measured best of 16/32/64/128 (fewer
-  // chunk sums shorten the last block's fold, longer chunks cost
-  // parallelism in the first phase)
-  const int chunk = 2 * kColChunk;
+  const int chunk = kColChunk;
   const int yblocks = (nparts + chunk - 1) / chunk;
   auto out = torch::empty({S}, parts.options());
   auto tmp = torch::empty({yblocks, S}, parts.options());
@@ -349,40 +291,32 @@ torch::Tensor col_reduce_full(torch::Tensor parts) {
   return out;
 }
 
-#define DISPATCH_FLOATING(TYPE, NAME, ...)                                   \
-  [&] {                                                                      \
-    if (TYPE == at::kBFloat16) {                                             \
-      using scalar_t = __hip_bfloat16;                                       \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kHalf) {                                          \
-      using scalar_t = __half;                                               \
-      constexpr int kVec = 8;                                                \
-      return __VA_ARGS__();                                                  \
-    } else if (TYPE == at::kFloat) {                                         \
-      using scalar_t = float;                                                \
-      constexpr int kVec = 4;                                                \
-      return __VA_ARGS__();                                                  \
-    } else {                                                                 \
-      TORCH_CHECK(false, NAME, ": unsupported dtype");                       \
-    }                                                                        \
-  }()
-
-// pick (threads, ITEMS) for the forward block-per-row shape
-template <typename LaunchFn>
-static void launch_by_items(int slices, LaunchFn&& fn) {
-  if (slices <= 256) {
-    fn(std::integral_constant<int, 1>{}, ((slices + 63) / 64) * 64);
-  } else if (slices <= 512) {
-    fn(std::integral_constant<int, 2>{}, 256);
-  } else if (slices <= 1024) {
-    fn(std::integral_constant<int, 2>{}, 512);
-  } else if (slices <= 2048) {
-    fn(std::integral_constant<int, 4>{}, 512);
-  } else {
-    TORCH_CHECK(slices <= 4096, "layernorm: H too large");
-    fn(std::integral_constant<int, 4>{}, 1024);
-  }
+// dgamma | dbeta (| dbias, when dx_src is defined) of the LN family
+// backward as one fp32 [nsl * H] vector: col_stats_kernel partials over
+// row chunks, folded by col_reduce_full.
+torch::Tensor col_stats(torch::Tensor dy, torch::Tensor z,
+                        torch::Tensor dx_src, torch::Tensor mean,
+                        torch::Tensor rstd) {
+  const int rows = z.size(0), H = z.size(1);
+  const int rows_per_chunk = 16;  // halves partial-buffer traffic; 16 independent loads/thread
+  const int n_chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
+  const bool has_bias = dx_src.defined();
+  auto part = torch::empty({n_chunks, (has_bias ? 3 : 2) * H},
+                           z.options().dtype(torch::kFloat32));
+  auto stream = at::hip::getCurrentHIPStream();
+  DISPATCH_ROW_DTYPE(z.scalar_type(), "col_stats", [&] {
+    const int threads = tmin(256, ((H / kVec + 63) / 64) * 64);
+    dim3 grid((H / kVec + threads - 1) / threads, n_chunks);
+    by_flag(has_bias, [&](auto bias_c) {
+      hipLaunchKernelGGL(
+          (col_stats_kernel<scalar_t, kVec, decltype(bias_c)::value>), grid,
+          dim3(threads), 0, stream, dptr<scalar_t>(dy), dptr<scalar_t>(z),
+          has_bias ? dptr<scalar_t>(dx_src) : nullptr, mean.data_ptr<float>(),
+          rstd.data_ptr<float>(), part.data_ptr<float>(), rows, H,
+          rows_per_chunk);
+    });
+  });
+  return col_reduce_full(part);
 }
 
 std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor gamma,
@@ -396,16 +330,15 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor gamma,
   auto mean = torch::empty({rows}, opts);
   auto rstd = torch::empty({rows}, opts);
   auto stream = at::hip::getCurrentHIPStream();
-  DISPATCH_FLOATING(x.scalar_type(), "ln_fwd", [&] {
+  DISPATCH_ROW_DTYPE(x.scalar_type(), "ln_fwd", [&] {
     TORCH_CHECK(H % kVec == 0, "ln_fwd: H must be a multiple of ", kVec);
-    launch_by_items(H / kVec, [&](auto items_c, int threads) {
-      hipLaunchKernelGGL((ln_fwd_kernel<scalar_t, kVec, decltype(items_c)::value>),
-                         dim3(rows), dim3(threads), 0, stream,
-                         reinterpret_cast<const scalar_t*>(x.data_ptr()),
-                         gamma_f.data_ptr<float>(), beta_f.data_ptr<float>(),
-                         reinterpret_cast<scalar_t*>(y.data_ptr()),
-                         mean.data_ptr<float>(), rstd.data_ptr<float>(), rows,
-                         H, static_cast<float>(eps));
+    launch_by_items("ln_fwd", H / kVec, [&](auto items_c, int threads) {
+      hipLaunchKernelGGL(
+          (ln_fwd_kernel<scalar_t, kVec, decltype(items_c)::value>),
+          dim3(rows), dim3(threads), 0, stream, dptr<scalar_t>(x),
+          gamma_f.data_ptr<float>(), beta_f.data_ptr<float>(),
+          dptr<scalar_t>(y), mean.data_ptr<float>(), rstd.data_ptr<float>(),
+          rows, H, static_cast<float>(eps));
     });
   });
   return {y, mean, rstd};
@@ -422,31 +355,19 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x,
   check_param("ln_bwd", "gamma", gamma, H);
   auto gamma_f = gamma.contiguous().to(torch::kFloat32);
   auto dx = torch::empty_like(x);
-  const int rows_per_chunk = 16;  // halves partial-buffer traffic; 16 independent loads/thread
-  const int n_chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
-  auto opts = x.options().dtype(torch::kFloat32);
-  auto part = torch::empty({n_chunks, 2 * H}, opts);
   auto stream = at::hip::getCurrentHIPStream();
-  DISPATCH_FLOATING(x.scalar_type(), "ln_bwd", [&] {
+  DISPATCH_ROW_DTYPE(x.scalar_type(), "ln_bwd", [&] {
     TORCH_CHECK(H % kVec == 0, "ln_bwd: H must be a multiple of ", kVec);
-    launch_by_items(H / kVec, [&](auto items_c, int threads) {
+    launch_by_items("ln_bwd", H / kVec, [&](auto items_c, int threads) {
       hipLaunchKernelGGL(
           (ln_bwd_dx_kernel<scalar_t, kVec, decltype(items_c)::value>),
-          dim3(rows), dim3(threads), 0, stream,
-          reinterpret_cast<const scalar_t*>(dy.data_ptr()),
-          reinterpret_cast<const scalar_t*>(x.data_ptr()),
-          gamma_f.data_ptr<float>(), mean.data_ptr<float>(),
-          rstd.data_ptr<float>(),
-          reinterpret_cast<scalar_t*>(dx.data_ptr()), rows, H);
+          dim3(rows), dim3(threads), 0, stream, dptr<scalar_t>(dy),
+          dptr<scalar_t>(x), gamma_f.data_ptr<float>(),
+          mean.data_ptr<float>(), rstd.data_ptr<float>(), dptr<scalar_t>(dx),
+          rows, H);
     });
-    launch_col_stats<scalar_t, kVec>(
-        reinterpret_cast<const scalar_t*>(dy.data_ptr()),
-        reinterpret_cast<const scalar_t*>(x.data_ptr()), nullptr,
-        mean.data_ptr<float>(), rstd.data_ptr<float>(),
-        part.data_ptr<float>(), rows, H, rows_per_chunk, n_chunks, false,
-        stream);
   });
-  auto dgb = col_reduce_full(part);
+  auto dgb = col_stats(dy, x, torch::Tensor(), mean, rstd);
   auto dgamma = dgb.narrow(0, 0, H);
   auto dbeta = dgb.narrow(0, H, H);
   if (gamma.scalar_type() != torch::kFloat32) {

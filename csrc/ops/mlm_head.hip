@@ -41,6 +41,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "../common.h"
+#include "../ops.h"
 #include "../mfma_types.h"
 
 namespace bpa {

@@ -20,6 +20,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "../common.h"
+#include "../ops.h"
 
 namespace bpa {
 

@@ -22,6 +22,7 @@
 #include <unordered_map>
 
 #include "../common.h"
+#include "../ops.h"
 
 namespace bpa {
 

@@ -12,18 +12,7 @@
 #include <utility>
 #include <vector>
 
-namespace bpa_tok {
-int64_t create_wordpiece(std::vector<std::string> vocab, std::string unk);
-std::pair<std::vector<std::string>, std::vector<int64_t>> encode_wordpiece(
-    int64_t handle, std::vector<std::string> words);
-int64_t create_bpe(std::vector<std::string> vocab,
-                   std::vector<std::string> merge_lines);
-std::pair<std::vector<std::string>, std::vector<int64_t>> encode_bpe(
-    int64_t handle, std::vector<std::string> pretokens);
-std::vector<std::string> train_bpe(std::vector<std::string> words,
-                                   std::vector<int64_t> counts,
-                                   int64_t num_merges);
-}  // namespace bpa_tok
+#include "../ops.h"  // built with BPA_TOK_ONLY: tokenizer prototypes only
 
 int main() {
   using namespace bpa_tok;

@@ -20,6 +20,8 @@
 #include <utility>
 #include <vector>
 
+#include "../ops.h"
+
 namespace bpa_tok {
 
 struct WordPieceModel {

@@ -96,7 +96,8 @@ def _same(o1, o2):
 # 2. shape and dtype sweep
 # ---------------------------------------------------------------------------
 # (H, rows). Slices = H / VEC (VEC 8 for 16-bit, 4 for fp32); the branch
-# of launch_by_items (layernorm.hip, copied in fused_residual.hip):
+# of launch_by_items (rowwise.h, shared by layernorm.hip and
+# fused_residual.hip):
 H_16BIT = [
     (64, 37),     # 8 slices: one wave, block_reduce's nwaves == 1 return
     (768, 37),    # 96 slices on 128 threads: last wave half filled
