@@ -169,12 +169,14 @@ class BertSelfOutput(nn.Module):
         self.LayerNorm = ops.FusedLayerNorm(config.hidden_size, eps=1e-12)
         self.dropout_prob = config.hidden_dropout_prob
 
-    def forward(self, hidden: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+    def forward(self, hidden: torch.Tensor, residual: torch.Tensor, fork: bool = False):
+        """``fork``: return the output as a pair of handles, one per
+        consumer (ops/fused_residual.py)."""
         y = ops.linear_nobias(hidden, self.dense.weight)  # bias in fusion
         return ops.fused_bias_dropout_residual_ln(
             y, self.dense.bias, residual,
             self.LayerNorm.weight, self.LayerNorm.bias,
-            self.dropout_prob, self.training,
+            self.dropout_prob, self.training, fork=fork,
         )
 
 
@@ -194,11 +196,14 @@ class BertAttention(nn.Module):
         self.dropout_prob = config.attention_probs_dropout_prob
 
     def forward(
-        self, x: torch.Tensor, seqlens: torch.Tensor, max_seqlen: int = 0
-    ) -> torch.Tensor:
+        self, x, seqlens: torch.Tensor, max_seqlen: int = 0, fork: bool = False
+    ):
         """Padded: x [B,S,H] with per-sequence lengths ``seqlens`` [B].
         Unpadded (``max_seqlen`` > 0): x [T_pad,H] packed, and
-        ``seqlens`` carries cu_seqlens [B+1]."""
+        ``seqlens`` carries cu_seqlens [B+1]. x may be the pair of handles
+        of a forked junction output: the first feeds QKV, the second the
+        residual. ``fork`` asks for this block's output as such a pair."""
+        x, x_res = x if isinstance(x, tuple) else (x, x)
         qkv = self.self(x)
         if max_seqlen:
             ctx = ops.fused_attention_varlen(
@@ -209,7 +214,7 @@ class BertAttention(nn.Module):
             ctx = ops.fused_attention(
                 qkv, seqlens, self.num_heads, self.dropout_prob, self.training
             )
-        return self.output(ctx, x)
+        return self.output(ctx, x_res, fork)
 
 
 class BertIntermediate(nn.Module):
@@ -230,12 +235,12 @@ class BertOutput(nn.Module):
         self.LayerNorm = ops.FusedLayerNorm(config.hidden_size, eps=1e-12)
         self.dropout_prob = config.hidden_dropout_prob
 
-    def forward(self, hidden: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
+    def forward(self, hidden: torch.Tensor, residual: torch.Tensor, fork: bool = False):
         y = ops.linear_nobias(hidden, self.dense.weight)
         return ops.fused_bias_dropout_residual_ln(
             y, self.dense.bias, residual,
             self.LayerNorm.weight, self.LayerNorm.bias,
-            self.dropout_prob, self.training,
+            self.dropout_prob, self.training, fork=fork,
         )
 
 
@@ -248,9 +253,13 @@ class BertLayer(nn.Module):
         self._ffn_gelu = config.hidden_act in ("gelu", "bias_gelu")
 
     def forward(
-        self, x: torch.Tensor, seqlens: torch.Tensor, max_seqlen: int = 0
-    ) -> torch.Tensor:
-        attn = self.attention(x, seqlens, max_seqlen)
+        self, x, seqlens: torch.Tensor, max_seqlen: int = 0, fork: bool = False
+    ):
+        """x: a tensor, or the pair a preceding layer returned with
+        ``fork=True`` (one handle for QKV, one for the residual). Inside
+        the layer the attention junction's output is always forked
+        between FFN1 and the FFN residual."""
+        attn, attn_res = self.attention(x, seqlens, max_seqlen, fork=True)
         if self._ffn_gelu and ops.ffn_supported(attn):
             # GELU folded into the FFN GEMM epilogues (ops/ffn.py);
             # FFN2's bias stays fused in the bdrl kernel below
@@ -261,12 +270,12 @@ class BertLayer(nn.Module):
                 self.output.dense.weight,
             )
             return ops.fused_bias_dropout_residual_ln(
-                y, self.output.dense.bias, attn,
+                y, self.output.dense.bias, attn_res,
                 self.output.LayerNorm.weight, self.output.LayerNorm.bias,
-                self.output.dropout_prob, self.training,
+                self.output.dropout_prob, self.training, fork=fork,
             )
         inter = self.intermediate(attn)
-        return self.output(inter, attn)
+        return self.output(inter, attn_res, fork)
 
 
 class BertEncoder(nn.Module):
@@ -287,8 +296,11 @@ class BertEncoder(nn.Module):
 
         def run(start, end):
             def custom(hidden, lens):
-                for layer in self.layer[start:end]:
-                    hidden = layer(hidden, lens, max_seqlen)
+                # forked junction outputs between the layers of a chunk;
+                # one tensor crosses the checkpoint boundary
+                for i in range(start, end):
+                    hidden = self.layer[i](hidden, lens, max_seqlen,
+                                           fork=i + 1 < end)
                 return hidden
 
             return custom
@@ -310,10 +322,14 @@ class BertEncoder(nn.Module):
         if self._checkpoint_activations:
             x = self._checkpointed_forward(x, seqlens, max_seqlen)
         else:
-            for layer in self.layer:
-                x = layer(x, seqlens, max_seqlen)
+            # every layer but the last hands its output on as a pair of
+            # handles (next QKV, next residual); the last layer's output
+            # goes to the heads as one tensor
+            last = len(self.layer) - 1
+            for i, layer in enumerate(self.layer):
+                x = layer(x, seqlens, max_seqlen, fork=i < last)
                 if self.output_all_encoded_layers:
-                    all_layers.append(x)
+                    all_layers.append(x[0] if i < last else x)
         if not self.output_all_encoded_layers or self._checkpoint_activations:
             all_layers.append(x)
         return all_layers

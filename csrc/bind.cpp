@@ -16,7 +16,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "hipblaslt dgrad GEMM with fused dGELU+bias-grad epilogue");
   m.def("gemm_gelu_aux_supported", &bpa::gemm_gelu_aux_supported);
   m.def("bias_dropout_residual_ln_fwd", &bpa::bias_dropout_residual_ln_fwd);
-  m.def("bias_dropout_residual_ln_bwd", &bpa::bias_dropout_residual_ln_bwd);
+  m.def("bias_dropout_residual_ln_bwd", &bpa::bias_dropout_residual_ln_bwd,
+        py::arg("dy"), py::arg("z"), py::arg("mask"), py::arg("gamma"),
+        py::arg("mean"), py::arg("rstd"), py::arg("p"), py::arg("has_bias"),
+        py::arg("dy2") = py::none());
   m.def("embedding_ln_dropout_fwd", &bpa::embedding_ln_dropout_fwd);
   m.def("embedding_ln_dropout_bwd", &bpa::embedding_ln_dropout_bwd);
   m.def("ce_fwd", &bpa::ce_fwd);

@@ -38,12 +38,8 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor bias);
 torch::Tensor col_sum(torch::Tensor x);
 // layernorm.hip, shared by the backward entry points: fold [nparts, S]
-// fp32 partials over rows in a fixed order; dgamma | dbeta (| dbias when
-// dx_src is defined) of the LayerNorm family as one fp32 [nsl * H] vector
+// fp32 partials over rows in a fixed order
 torch::Tensor col_reduce_full(torch::Tensor parts);
-torch::Tensor col_stats(torch::Tensor dy, torch::Tensor z,
-                        torch::Tensor dx_src, torch::Tensor mean,
-                        torch::Tensor rstd);
 std::vector<torch::Tensor> gemm_bias_gelu_fwd(torch::Tensor x,
                                               torch::Tensor w1,
                                               torch::Tensor b1);
@@ -57,7 +53,8 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
     int64_t seed, int64_t offset);
 std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
     torch::Tensor dy, torch::Tensor z, torch::Tensor mask, torch::Tensor gamma,
-    torch::Tensor mean, torch::Tensor rstd, double p, bool has_bias);
+    torch::Tensor mean, torch::Tensor rstd, double p, bool has_bias,
+    c10::optional<torch::Tensor> dy2);
 std::vector<torch::Tensor> embedding_ln_dropout_fwd(
     torch::Tensor ids, c10::optional<torch::Tensor> tt, torch::Tensor word,
     torch::Tensor pos, c10::optional<torch::Tensor> tok, torch::Tensor gamma,

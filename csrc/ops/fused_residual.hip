@@ -10,9 +10,11 @@
 // * forward: one BLOCK per row; x/residual loaded once into registers,
 //   z kept in registers through the mean/var block reduction, y written
 //   from registers — no re-read of z after the reduction.
-// * backward: one BLOCK per row writes dz_res and dx from registers;
-//   dgamma/dbeta/dbias come from the col_stats pass shared with ln_bwd
-//   (layernorm.hip), which reads dy, z and the dx just written.
+// * backward: one pass (ln_bwd_rows_kernel, rowwise.h, shared with
+//   ln_bwd). A block owns a group of consecutive rows; dz_res and dx are
+//   written from registers and dgamma/dbeta/dbias are accumulated in the
+//   same registers across the block's rows; the [nblocks, 3H] partials
+//   are folded by col_reduce_full (layernorm.hip).
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -70,63 +72,6 @@ __global__ void bdrl_fwd_kernel(
   ln_affine_store<T, VEC, ITEMS>(zv, cols, st, gamma, beta, y + base, H);
 }
 
-// backward dx/dz: one BLOCK per row (mirror of bdrl_fwd_kernel); dy/z/
-// mask loaded once into registers, s1/s2 via block reduce, dz_res and
-// dx written from registers. dgamma/dbeta/dbias partials come from the
-// shared streaming col_stats_kernel (layernorm.hip) reading dy, z and
-// the dx this kernel wrote.
-template <typename T, int VEC, int ITEMS, bool TRAIN_DROP>
-__global__ void bdrl_bwd_dx_kernel(
-    const T* __restrict__ dy, const T* __restrict__ z,
-    const uint8_t* __restrict__ mask, const float* __restrict__ gamma,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    T* __restrict__ dx, T* __restrict__ dz_res, int rows, int H, float p) {
-  __shared__ float red[32];
-  const int row = blockIdx.x;
-  if (row >= rows) return;
-  const int64_t base = static_cast<int64_t>(row) * H;
-  const float mu = mean[row], rs = rstd[row];
-  const float keep_scale = TRAIN_DROP ? 1.0f / (1.0f - p) : 1.0f;
-
-  float dw[ITEMS][VEC], zh[ITEMS][VEC];
-  uint8_t mv[ITEMS][VEC];
-  int cols[ITEMS];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int c = (i * blockDim.x + threadIdx.x) * VEC;
-    cols[i] = c;
-    if (c < H) {
-      T dt[VEC], zt[VEC];
-      load_slice(dy + base + c, dt);
-      load_slice(z + base + c, zt);
-      if (TRAIN_DROP) load_mask(mask + base + c, mv[i]);
-#pragma unroll
-      for (int k = 0; k < VEC; ++k)
-        ln_bwd_elem(zt[k], dt[k], &gamma[c + k], mu, rs, dw[i][k], zh[i][k],
-                    s1, s2);
-    }
-  }
-  ln_bwd_row_means(s1, s2, H, red);
-#pragma unroll
-  for (int i = 0; i < ITEMS; ++i) {
-    const int c = cols[i];
-    if (c < H) {
-      T dzo[VEC], dxo[VEC];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        const float dzk = ln_bwd_dz(dw[i][k], zh[i][k], rs, s1, s2);
-        dzo[k] = DTraits<T>::from_f32(dzk);  // grad to residual input
-        const float dxk =
-            TRAIN_DROP ? (mv[i][k] ? dzk * keep_scale : 0.f) : dzk;
-        dxo[k] = DTraits<T>::from_f32(dxk);
-      }
-      store_slice(dz_res + base + c, dzo);
-      store_slice(dx + base + c, dxo);
-    }
-  }
-}
-
 std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
     torch::Tensor x, c10::optional<torch::Tensor> bias, torch::Tensor residual,
     torch::Tensor gamma, torch::Tensor beta, double p, double eps,
@@ -178,9 +123,15 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
 
 std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
     torch::Tensor dy, torch::Tensor z, torch::Tensor mask, torch::Tensor gamma,
-    torch::Tensor mean, torch::Tensor rstd, double p, bool has_bias) {
+    torch::Tensor mean, torch::Tensor rstd, double p, bool has_bias,
+    c10::optional<torch::Tensor> dy2) {
   check_rows_2d("bdrl_bwd", "z", z);
   check_like("bdrl_bwd", "dy", dy, "z", z);
+  if (dy2.has_value()) {
+    TORCH_CHECK(dy2->device() == z.device(), "bdrl_bwd: dy2 device ",
+                dy2->device(), " does not match z device ", z.device());
+    check_like("bdrl_bwd", "dy2", *dy2, "z", z);
+  }
   const int rows = z.size(0), H = z.size(1);
   check_row_stat("bdrl_bwd", "mean", mean, rows);
   check_row_stat("bdrl_bwd", "rstd", rstd, rows);
@@ -190,24 +141,15 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
   auto dx = torch::empty_like(z);
   auto dz_res = torch::empty_like(z);
   auto fopts = z.options().dtype(torch::kFloat32);
-  const bool train_drop = p > 0.0;
   auto stream = at::hip::getCurrentHIPStream();
+  torch::Tensor part;
   DISPATCH_ROW_DTYPE(z.scalar_type(), "bdrl_bwd", [&] {
     TORCH_CHECK(H % kVec == 0, "bdrl_bwd: H % ", kVec, " != 0");
-    launch_by_items("bdrl_bwd", H / kVec, [&](auto items_c, int threads) {
-      by_flag(train_drop, [&](auto train_c) {
-        hipLaunchKernelGGL(
-            (bdrl_bwd_dx_kernel<scalar_t, kVec, decltype(items_c)::value,
-                                decltype(train_c)::value>),
-            dim3(rows), dim3(threads), 0, stream, dptr<scalar_t>(dy),
-            dptr<scalar_t>(z), train_drop ? mask.data_ptr<uint8_t>() : nullptr,
-            gamma_f.data_ptr<float>(), mean.data_ptr<float>(),
-            rstd.data_ptr<float>(), dptr<scalar_t>(dx),
-            dptr<scalar_t>(dz_res), rows, H, static_cast<float>(p));
-      });
-    });
+    part = ln_bwd_rows<scalar_t, kVec, true>(
+        "bdrl_bwd", dy, dy2.has_value() ? *dy2 : torch::Tensor(), z, mask,
+        gamma_f, mean, rstd, dx, dz_res, p, has_bias, stream);
   });
-  auto out = col_stats(dy, z, has_bias ? dx : torch::Tensor(), mean, rstd);
+  auto out = col_reduce_full(part);
   auto dgamma = out.narrow(0, 0, H).contiguous();
   auto dbeta = out.narrow(0, H, H).contiguous();
   auto dbias =

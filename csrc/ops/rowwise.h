@@ -9,6 +9,7 @@
 
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "../common.h"
@@ -187,20 +188,26 @@ __device__ __forceinline__ void ln_affine_store(
 // ---------------------------------------------------------------------------
 // LayerNorm backward row core: dw = dy * gamma, xh = (x - mu) * rs,
 // s1 = sum(dw * xh), s2 = sum(dw) over the thread's slices; then
-// dz = rs * (dw - mean(dw) - xh * mean(dw * xh)). x, dy and gamma come in
-// unconverted and unloaded, so that every operation keeps its place.
+// dz = rs * (dw - mean(dw) - xh * mean(dw * xh)). x comes in unconverted,
+// so that every operation keeps its place. Which products are fused into
+// an fma is spelled out (only the one in dz), with contraction off
+// otherwise: left to the compiler it differs from one instantiation of a
+// kernel to the next, and dx has to be the same whichever of them
+// computes it.
 // ---------------------------------------------------------------------------
 template <typename T>
-__device__ __forceinline__ void ln_bwd_elem(T x, T dy, const float* gamma,
+__device__ __forceinline__ void ln_bwd_elem(T x, float dy, float gamma,
                                             float mu, float rs, float& dw,
                                             float& xh, float& s1, float& s2) {
+#pragma clang fp contract(off)
   xh = (DTraits<T>::to_f32(x) - mu) * rs;
-  dw = DTraits<T>::to_f32(dy) * *gamma;
-  s1 += dw * xh;
+  dw = dy * gamma;
+  s1 += dw * xh;  // product rounded, then added: not an fma
   s2 += dw;
 }
 
-// block-reduces s1, s2 to their row means; red: 32 floats, single-use
+// block-reduces s1, s2 to their row means over the blockDim.x threads of
+// one row; red: 32 floats, not reused before the block's next barrier
 __device__ __forceinline__ void ln_bwd_row_means(float& s1, float& s2, int H,
                                                  float* red) {
   block_reduce_sum2(s1, s2, red);
@@ -210,7 +217,260 @@ __device__ __forceinline__ void ln_bwd_row_means(float& s1, float& s2, int H,
 
 __device__ __forceinline__ float ln_bwd_dz(float dw, float xh, float rs,
                                            float s1, float s2) {
-  return rs * (dw - s2 - xh * s1);
+#pragma clang fp contract(off)
+  return rs * __builtin_fmaf(-xh, s1, dw - s2);
+}
+
+// ---------------------------------------------------------------------------
+// LayerNorm-family backward, one pass: dx (and the junction's dz_res) plus
+// the column gradients. A block is blockDim.y row lanes of blockDim.x
+// threads (the launch_by_items mapping) and owns rows_per_block
+// consecutive rows; lane y takes rows r_begin + y, + blockDim.y, ... so
+// that blockDim.y rows are in flight side by side, and every thread sees
+// the same columns in every row. It carries fp32 sums of dy * xh
+// (dgamma), dy (dbeta) and, with HAS_BIAS, of dx as stored (dbias) across
+// its rows; at the end the lanes are added in y order through the LDS
+// slab and the block stores one [nsl * H] row of `part`. The caller folds
+// the part rows with col_reduce_full: every order is fixed, no atomics.
+//
+// JUNCTION: bias + dropout + residual + LN (x is the saved z; writes
+// dz_res and dx = dropout'(dz)); otherwise plain LN (writes dx only).
+// HAS_DY2: the upstream gradient is dy + dy2, summed in fp32 on load.
+// Narrow rows (kPipe) keep gamma in registers and load the lane's next
+// row before the current row's block reduction.
+// ---------------------------------------------------------------------------
+constexpr int kRowGroupThreads = 512;  // blockDim.x * blockDim.y, at most
+constexpr int kRowGroupBlocks = 512;   // grid, at most
+constexpr int kRowGroupMinRows = 2;    // rows per lane, at least
+
+template <typename T, int VEC, int ITEMS, bool DROP, bool DY2>
+struct LnBwdRow {
+  T dy[ITEMS][VEC], x[ITEMS][VEC];
+  T dy2[DY2 ? ITEMS : 1][VEC];
+  uint8_t keep[DROP ? ITEMS : 1][VEC];
+  float mu, rs;
+};
+
+template <typename T, int VEC, int ITEMS, bool JUNCTION, bool TRAIN_DROP,
+          bool HAS_BIAS, bool HAS_DY2>
+__global__ void
+__launch_bounds__(ITEMS <= 2 ? kRowGroupThreads : 1024, ITEMS == 2 ? 2 : 4)
+ln_bwd_rows_kernel(
+    const T* __restrict__ dy, const T* __restrict__ dy2,
+    const T* __restrict__ x, const uint8_t* __restrict__ mask,
+    const float* __restrict__ gamma, const float* __restrict__ mean,
+    const float* __restrict__ rstd, T* __restrict__ dx,
+    T* __restrict__ dz_res, float* __restrict__ part, int rows, int H,
+    int rows_per_block, float p) {
+  static_assert(JUNCTION || !(TRAIN_DROP || HAS_BIAS || HAS_DY2), "");
+  constexpr bool kPipe = ITEMS * VEC <= 8;
+  constexpr int NSL = HAS_BIAS ? 3 : 2;
+  using Row = LnBwdRow<T, VEC, ITEMS, TRAIN_DROP, HAS_DY2>;
+  extern __shared__ float slab[];
+  __shared__ float red[2][kRowGroupThreads / WAVE_SIZE][32];
+  const int lanes = blockDim.y, y = threadIdx.y;
+  const int r_begin = blockIdx.x * rows_per_block;
+  const int r_end = min(r_begin + rows_per_block, rows);
+  const float keep_scale = TRAIN_DROP ? 1.0f / (1.0f - p) : 1.0f;
+
+  int cols[ITEMS];
+  float g[kPipe ? ITEMS : 1][VEC];
+#pragma unroll
+  for (int i = 0; i < ITEMS; ++i) {
+    cols[i] = (i * blockDim.x + threadIdx.x) * VEC;
+    if (kPipe && cols[i] < H) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) g[i][k] = gamma[cols[i] + k];
+    }
+  }
+  auto load_row = [&](Row& r, int row) {
+    const int64_t base = static_cast<int64_t>(row) * H;
+    r.mu = mean[row];
+    r.rs = rstd[row];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+      const int c = cols[i];
+      if (c < H) {
+        load_slice(dy + base + c, r.dy[i]);
+        if (HAS_DY2) load_slice(dy2 + base + c, r.dy2[i]);
+        load_slice(x + base + c, r.x[i]);
+        if (TRAIN_DROP) load_mask(mask + base + c, r.keep[i]);
+      }
+    }
+  };
+
+  float acc[NSL][ITEMS][VEC] = {};
+  Row cur, nxt;
+  int row = r_begin + y;
+  if (kPipe && row < r_end) load_row(cur, row);
+  for (int it = 0; r_begin + it * lanes < r_end; ++it, row += lanes) {
+    const bool valid = row < r_end;
+    if (kPipe) {
+      if (row + lanes < r_end) load_row(nxt, row + lanes);
+    } else if (valid) {
+      load_row(cur, row);
+    }
+    float dw[ITEMS][VEC], xh[ITEMS][VEC];
+    float s1 = 0.f, s2 = 0.f;
+    if (valid) {
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) {
+        const int c = cols[i];
+        if (c < H) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            float d = DTraits<T>::to_f32(cur.dy[i][k]);
+            if (HAS_DY2) d += DTraits<T>::to_f32(cur.dy2[i][k]);
+            const float gk = kPipe ? g[i][k] : gamma[c + k];
+            ln_bwd_elem(cur.x[i][k], d, gk, cur.mu, cur.rs, dw[i][k],
+                        xh[i][k], s1, s2);
+            acc[0][i][k] += d * xh[i][k];
+            acc[1][i][k] += d;
+          }
+        }
+      }
+    }
+    // the buffer of iteration it - 2: every wave has passed the barrier of
+    // it - 1 since it read that one
+    ln_bwd_row_means(s1, s2, H, red[it & 1][y]);
+    if (valid) {
+      const int64_t base = static_cast<int64_t>(row) * H;
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) {
+        const int c = cols[i];
+        if (c < H) {
+          T dzo[VEC], dxo[VEC];
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            const float dzk = ln_bwd_dz(dw[i][k], xh[i][k], cur.rs, s1, s2);
+            dzo[k] = DTraits<T>::from_f32(dzk);  // grad to residual input
+            if (JUNCTION) {
+              float dxk = dzk;
+              if (TRAIN_DROP) {
+                dxk = cur.keep[i][k] ? dzk * keep_scale : 0.f;
+                // keep the product an fp32 value of its own: folded into
+                // the conversion (v_fma_mixlo_f16) it is rounded once, not
+                // twice, and whether the compiler folds it differs from
+                // one instantiation to the next
+                asm("" : "+v"(dxk));
+              }
+              dxo[k] = DTraits<T>::from_f32(dxk);
+              // the value as stored: dbias stays the column sum of dx
+              if (HAS_BIAS) acc[NSL - 1][i][k] += DTraits<T>::to_f32(dxo[k]);
+            }
+          }
+          if (JUNCTION) {
+            store_slice(dz_res + base + c, dzo);
+            store_slice(dx + base + c, dxo);
+          } else {
+            store_slice(dx + base + c, dzo);
+          }
+        }
+      }
+    }
+    if (kPipe) cur = nxt;
+  }
+
+  float* out = part + static_cast<int64_t>(blockIdx.x) * NSL * H;
+#pragma unroll
+  for (int sl = 0; sl < NSL; ++sl) {
+    if (lanes == 1) {
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) {
+        if (cols[i] < H) {
+#pragma unroll
+          for (int k = 0; k < VEC; ++k)
+            out[sl * H + cols[i] + k] = acc[sl][i][k];
+        }
+      }
+      continue;
+    }
+    // slab[lane][item][k][thread]: consecutive threads, consecutive words
+    if (sl > 0) __syncthreads();
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k)
+        slab[((y * ITEMS + i) * VEC + k) * blockDim.x + threadIdx.x] =
+            acc[sl][i][k];
+    }
+    __syncthreads();
+    if (y == sl % lanes) {
+#pragma unroll
+      for (int i = 0; i < ITEMS; ++i) {
+        if (cols[i] < H) {
+          float tot[VEC] = {};
+          for (int j = 0; j < lanes; ++j) {
+#pragma unroll
+            for (int k = 0; k < VEC; ++k)
+              tot[k] +=
+                  slab[((j * ITEMS + i) * VEC + k) * blockDim.x + threadIdx.x];
+          }
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) out[sl * H + cols[i] + k] = tot[k];
+        }
+      }
+    }
+  }
+}
+
+// Launches ln_bwd_rows_kernel<T, VEC, ..., JUNCTION, ...> over [rows, H]
+// and returns its fp32 partials [nblocks, nsl * H] (dgamma | dbeta |
+// dbias), to be folded by col_reduce_full. Row lanes fill the block up to
+// kRowGroupThreads; a lane takes the fewest rows that keep the grid within
+// kRowGroupBlocks, and at least kRowGroupMinRows (sweep: docs/KERNELS.md).
+// dy2 and mask may be undefined (no second gradient, no dropout); dz_res
+// only with JUNCTION.
+template <typename T, int VEC, bool JUNCTION>
+inline torch::Tensor ln_bwd_rows(const char* op, const torch::Tensor& dy,
+                                 const torch::Tensor& dy2,
+                                 const torch::Tensor& x,
+                                 const torch::Tensor& mask,
+                                 const torch::Tensor& gamma_f,
+                                 const torch::Tensor& mean,
+                                 const torch::Tensor& rstd, torch::Tensor& dx,
+                                 torch::Tensor& dz_res, double p,
+                                 bool has_bias, hipStream_t stream) {
+  const int rows = x.size(0), H = x.size(1);
+  const int nsl = has_bias ? 3 : 2;
+  auto fopts = x.options().dtype(torch::kFloat32);
+  if (rows == 0) return torch::zeros({1, nsl * H}, fopts);
+  const bool train_drop = JUNCTION && p > 0.0;
+  const bool has_dy2 = dy2.defined();
+  torch::Tensor part;
+  launch_by_items(op, H / VEC, [&](auto items_c, int threads) {
+    constexpr int ITEMS = decltype(items_c)::value;
+    const int lanes =
+        threads >= kRowGroupThreads ? 1 : kRowGroupThreads / threads;
+    const int groups = (rows + lanes - 1) / lanes;
+    const int rows_per_lane = std::max(
+        kRowGroupMinRows, (groups + kRowGroupBlocks - 1) / kRowGroupBlocks);
+    const int rows_per_block = rows_per_lane * lanes;
+    const int nblocks = (rows + rows_per_block - 1) / rows_per_block;
+    part = torch::empty({nblocks, nsl * H}, fopts);
+    const size_t lds =
+        lanes > 1 ? sizeof(float) * lanes * threads * ITEMS * VEC : 0;
+    by_flag(train_drop, [&](auto train_c) {
+      by_flag(has_bias, [&](auto bias_c) {
+        by_flag(has_dy2, [&](auto dy2_c) {
+          constexpr bool kTrain = JUNCTION && decltype(train_c)::value;
+          constexpr bool kBias = JUNCTION && decltype(bias_c)::value;
+          constexpr bool kDy2 = JUNCTION && decltype(dy2_c)::value;
+          hipLaunchKernelGGL(
+              (ln_bwd_rows_kernel<T, VEC, ITEMS, JUNCTION, kTrain, kBias,
+                                  kDy2>),
+              dim3(nblocks), dim3(threads, lanes), lds, stream, dptr<T>(dy),
+              kDy2 ? dptr<T>(dy2) : nullptr, dptr<T>(x),
+              kTrain ? mask.data_ptr<uint8_t>() : nullptr,
+              gamma_f.data_ptr<float>(), mean.data_ptr<float>(),
+              rstd.data_ptr<float>(), dptr<T>(dx),
+              JUNCTION ? dptr<T>(dz_res) : nullptr, part.data_ptr<float>(),
+              rows, H, rows_per_block, static_cast<float>(p));
+        });
+      });
+    });
+  });
+  return part;
 }
 
 }  // namespace bpa
