@@ -1,7 +1,7 @@
-// Host-side operand checks shared by the row-wise backward entry points.
-// The kernels reinterpret every operand as the dtype of the saved
-// activation and index it by that tensor's shape, so a mismatch reads or
-// writes out of bounds; these run before any launch.
+// Host-side operand checks shared by the row-wise and attention backward
+// entry points. The kernels reinterpret every operand as the dtype of
+// the saved activation and index it by that tensor's shape, so a
+// mismatch reads or writes out of bounds; these run before any launch.
 #pragma once
 
 #include <torch/extension.h>
@@ -47,6 +47,19 @@ inline void check_drop_mask(const char* op, const torch::Tensor& mask,
                   mask.is_contiguous(),
               op, ": mask must be contiguous [", rows, ", ", H, "], got ",
               mask.sizes());
+}
+
+// bit-packed attention keep-mask: one bit per score of `heads` [S, S]
+// score matrices, as int32 words, every row padded to whole words
+inline void check_bit_mask(const char* op, const torch::Tensor& mask,
+                           int64_t heads, int64_t S) {
+  TORCH_CHECK(mask.scalar_type() == torch::kInt32, op,
+              ": keep-mask dtype ", mask.scalar_type(), " must be ",
+              torch::kInt32);
+  const int64_t Sw = (S + 31) / 32;
+  TORCH_CHECK(mask.numel() == heads * S * Sw && mask.is_contiguous(), op,
+              ": keep-mask must be contiguous [", heads, ", ", S, ", ", Sw,
+              "], got ", mask.sizes());
 }
 
 // fp32 per-column parameter of length H (after the entry point's cast)

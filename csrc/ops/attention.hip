@@ -5,57 +5,57 @@
 // v_mfma_f32_16x16x32_bf16 / v_mfma_f32_16x16x32_f16 (one source,
 // templated on the 16-bit element type - csrc/mfma_types.h):
 //
-// Forward: grid (S/128 q-tiles, B*heads); 4 waves/block, 2x16 q-rows
-// per wave. K and V staged NATURALLY in LDS (K at a 72-elem stride for
-// conflict-free b64 row reads; V at an 80-elem stride for conflict-free
-// ds_read_b64_tr_b16 hardware-transpose fragment reads - no transposed
-// image is ever built); online softmax with the swapped-QK^T trick
-// (S^T = mfma(K, Q)) so each lane's P scores chain directly into the
-// PV A-fragment; the padding mask enters as per-sequence valid
-// lengths. Dropout keep-masks
-// are pre-generated once per forward by dropout_mask_kernel (Philox
-// 4x32-10, one BIT per score, rows padded to whole 32-bit words) and
-// the [B*NH, S, ceil(S/32)] word tensor is read by forward and both
-// backward kernels — measurably cheaper than regenerating the RNG
-// stream in each of the three consumers, and 8x less mask traffic
-// than the byte-mask variant.
-//
-// Backward (flash-2 style, atomic-free): two MFMA kernels.
-// * attn_bwd_kernel: grid (S/64 kv-tiles, B*heads); each block owns one
-//   K/V tile, loops over q-tiles; recomputes P from the saved
-//   logsumexp; accumulates dK/dV in registers, written once,
+// Device side, five kernels:
+// * dropout_mask_kernel: Philox 4x32-10 keep-mask, one BIT per score,
+//   rows padded to whole 32-bit words. Generated once per forward; the
+//   [B*NH, S, ceil(S/32)] word tensor is read by the forward and both
+//   backward kernels - cheaper than regenerating the RNG stream in each
+//   of the three consumers, and 8x less traffic than a byte mask.
+// * attn_fwd_kernel: grid (ceil(S/128) q-tiles, B*heads); 4 waves per
+//   block, 2x16 q-rows per wave. K and V are both staged NATURALLY in
+//   LDS, 64 rows per key tile (K at a 72-element stride for conflict-
+//   free b64 row reads, V at an 80-element stride for conflict-free
+//   ds_read_b64_tr_b16 transpose reads - no transposed image is ever
+//   built); online softmax with the swapped-QK^T trick
+//   (S^T = mfma(K, Q)) so each lane's P scores chain directly into the
+//   PV A-fragment; the padding mask enters as per-sequence lengths.
+// * attn_delta_kernel (and its packed twin): delta = rowsum(dO * O).
+// * attn_bwd_kernel: grid (ceil(S/128) key tiles, B*heads); each block
+//   owns 128 keys, loops over 64-row q-tiles, recomputes P from the
+//   saved logsumexp and accumulates dK/dV in registers, written once,
 //   exclusively, straight into dqkv.
-// * attn_dq_kernel: grid (S/64 q-tiles, B*heads); mirrors the forward's
-//   wave-owns-q structure, recomputes S^T/dP^T per K/V tile and chains
-//   dS^T fragments into dQ += dS.K MFMAs against K^T staged in LDS —
-//   dQ lands in registers and is written once (the previous design
-//   pushed ~1k fp32 atomicAdds per wave per q-iter into an fp32
-//   workspace plus a pack kernel; that was the backward bottleneck).
+// * attn_dq_kernel: grid (ceil(S/128) q-tiles, B*heads); mirrors the
+//   forward's wave-owns-q structure, recomputes S^T/dP^T per 64-row K/V
+//   tile and chains dS^T fragments into dQ += dS.K against K^T read
+//   with the transpose read; dQ is written once. No atomics anywhere.
+//
+// Each MFMA kernel's dynamic-LDS carve-up is one constexpr layout
+// (AttnFwdLds / AttnDqLds / AttnBwdLds) that the kernel and its launch
+// both read. The fragment builders live in csrc/mfma_frag.h.
 //
 // Variable-length (packed) layout: the three MFMA kernels take a
 // `bool VARLEN` template parameter. With it the batch is one
 // [T_pad, 3H] matrix of back-to-back sequences addressed through
 // cu_seqlens[B+1]; each sequence's own length bounds its loads, stores
 // and tile loops, so padded rows are neither computed nor read (see
-// seq_row0/seq_rows below and the attention_varlen_* host wrappers).
-// VARLEN=false is the padded layout described above, unchanged.
+// seq_row0/seq_rows). VARLEN=false is the padded [B, S, 3H] layout.
 //
-// Fragment convention (consistent A/B slot mapping):
-//   A[i][k]/B[k][j]: i|j = lane&15, k = (lane>>4)*4 + (e&3) + 16*(e>>2)
-//   C/D[i][j]:       j = lane&15,   i = (lane>>4)*4 + reg
-// Only A/B consistency matters for correctness (the contraction is
-// permutation-invariant when both sides agree); C/D is the documented
-// gfx950 layout.
+// Host side: attn_launch_fwd / attn_launch_bwd own mask generation, the
+// grids, LDS sizes and the TRAIN_DROP choice for both layouts. The four
+// entry points (attention_fwd/bwd, attention_varlen_fwd/bwd) check
+// their operands, allocate in their layout and dispatch on the dtype.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
 #include <cmath>
+#include <type_traits>
 #include <utility>
 
+#include "../checks.h"
 #include "../common.h"
 #include "../ops.h"
-#include "../mfma_types.h"
+#include "../mfma_frag.h"
 
 namespace bpa {
 
@@ -75,45 +75,58 @@ constexpr int kStride = 64 + kPad;
 // gcd(stride_dw,64)=4, tr needs gcd=8).
 constexpr int kTrStride = 80;
 
-// Build an A/B fragment from a row-major 16-bit row pointer: elements at
-// k = base + g*4 + (e&3) + 16*(e>>2), loaded as two 8-byte chunks.
+// Dynamic-LDS layouts of the three MFMA kernels: byte offsets of each
+// region, in order, and the total the launch asks for. The kernel's
+// pointer carve-up and the host's launch both read these; no size is
+// written out anywhere else.
 template <typename T>
-__device__ __forceinline__ typename Mfma16<T>::frag frag_row(const T* row,
-                                                             int base,
-                                                             int g) {
-  union {
-    typename Mfma16<T>::frag v;
-    uint2 u[2];
-  } r;
-  r.u[0] = *reinterpret_cast<const uint2*>(row + base + g * 4);
-  r.u[1] = *reinterpret_cast<const uint2*>(row + base + 16 + g * 4);
-  return r.v;
-}
+struct AttnFwdLds {
+  static constexpr size_t k = 0;                                  // T [64][kStride]
+  static constexpr size_t v = k + 64 * kStride * sizeof(T);       // T [64][kTrStride], tr-read
+  static constexpr size_t alpha = v + 64 * kTrStride * sizeof(T); // float [4][2][16]
+  static constexpr size_t stat = alpha + 4 * 2 * 16 * sizeof(float);  // float [4][2][16]
+  // keep-mask words of the current kv-tile, [128 q][2 words]
+  static constexpr size_t mask = stat + 4 * 2 * 16 * sizeof(float);
+  static constexpr size_t bytes = mask + 128 * 2 * sizeof(uint32_t);
+};
 
-// Transposed A/B fragment via gfx950's hardware transpose read, straight
-// from a NATURAL row-major [rows][kTrStride] bf16 LDS image: element
-// e = M[rb + g*4 + (e&3) + 16*(e>>2)][cb + li] - i.e. the fragment the
-// old code read from a separately-built transposed image. Semantics
-// probe-verified on hardware (tr16_probe): within each 16-lane group,
-// out[lane i][j] = mem[addr_of_lane(4j + (i>>2)) + (i&3)], so lane
-// (g, t) points at 4 contiguous elements of row rb + g*4 + (t>>2) and
-// the instruction delivers the group-transposed fragment. Replaces the
-// per-thread 16x ds_write_b16 transpose scatter at staging time.
 template <typename T>
-__device__ __forceinline__ typename Mfma16<T>::frag frag_tr(const T* img,
-                                                            int rb, int cb) {
-  using Tr = Mfma16<T>;
-  const int lane = threadIdx.x & 63;
-  const int g = (lane >> 4) & 3, t = lane & 15;
-  const T* p0 =
-      img + (rb + g * 4 + (t >> 2)) * kTrStride + cb + (t & 3) * 4;
-  union {
-    typename Tr::frag v;
-    typename Tr::tr4 h[2];
-  } r;
-  r.h[0] = Tr::tr_read(p0);
-  r.h[1] = Tr::tr_read(p0 + 16 * kTrStride);
-  return r.v;
+struct AttnDqLds {
+  static constexpr size_t k = 0;                                 // T [64][kTrStride], row- and tr-read
+  static constexpr size_t v = k + 64 * kTrStride * sizeof(T);    // T [64][kStride]
+  static constexpr size_t mask = v + 64 * kStride * sizeof(T);   // uint32 [128 q][2 words]
+  static constexpr size_t bytes = mask + 128 * 2 * sizeof(uint32_t);
+};
+
+// K/V hold 128 rows for the whole q-loop, Q/dO 64 rows per q-tile:
+// 57.5 KiB, for which the launch raises the kernel's dynamic-LDS limit
+// with hipFuncSetAttribute (MI355X has 160 KB per CU).
+template <typename T>
+struct AttnBwdLds {
+  static constexpr size_t k = 0;                                 // T [128][kStride]
+  static constexpr size_t v = k + 128 * kStride * sizeof(T);     // T [128][kStride]
+  static constexpr size_t q = v + 128 * kStride * sizeof(T);     // T [64][kTrStride], row- and tr-read
+  static constexpr size_t d_o = q + 64 * kTrStride * sizeof(T);  // T [64][kTrStride], row- and tr-read
+  static constexpr size_t lse = d_o + 64 * kTrStride * sizeof(T);  // float [64]
+  static constexpr size_t delta = lse + 64 * sizeof(float);        // float [64]
+  // keep-mask tile [64 q][128 keys] as bits, [4 words][64 q]
+  static constexpr size_t mask = delta + 64 * sizeof(float);
+  static constexpr size_t bytes = mask + 4 * 64 * sizeof(uint32_t);
+};
+
+static_assert(AttnFwdLds<__bf16>::bytes == 21504 &&
+                  AttnFwdLds<_Float16>::bytes == 21504,
+              "attn_fwd_kernel LDS layout moved");
+static_assert(AttnDqLds<__bf16>::bytes == 20480 &&
+                  AttnDqLds<_Float16>::bytes == 20480,
+              "attn_dq_kernel LDS layout moved");
+static_assert(AttnBwdLds<__bf16>::bytes == 58880 &&
+                  AttnBwdLds<_Float16>::bytes == 58880,
+              "attn_bwd_kernel LDS layout moved");
+
+template <typename U>
+__device__ __forceinline__ U* lds_at(char* smem, size_t byte_off) {
+  return reinterpret_cast<U*>(smem + byte_off);
 }
 
 // Dropout keep-mask generation, BIT-packed: one keep decision per BIT
@@ -183,6 +196,49 @@ __device__ __forceinline__ int seq_rows(const int* __restrict__ seqlens,
   return S;
 }
 
+// Stage key rows k0..k0+63 of K and V into natural row-major LDS images
+// at row strides KS and VS, zero past the sequence's row bound L. 256
+// threads: 4 per row, 16 columns each.
+template <int KS, int VS, typename T>
+__device__ __forceinline__ void stage_kv_tile(T* K_lds, T* V_lds,
+                                              const T* kbase, const T* vbase,
+                                              int k0, int L, int rs3,
+                                              int tid) {
+  const int row = tid >> 2, colc = (tid & 3) * 16;
+  const int krow = k0 + row;
+  if (krow < L) {
+    const uint4* ks = reinterpret_cast<const uint4*>(
+        kbase + static_cast<int64_t>(krow) * rs3 + colc);
+    *reinterpret_cast<uint4*>(&K_lds[row * KS + colc]) = ks[0];
+    *reinterpret_cast<uint4*>(&K_lds[row * KS + colc + 8]) = ks[1];
+    const uint4* vs = reinterpret_cast<const uint4*>(
+        vbase + static_cast<int64_t>(krow) * rs3 + colc);
+    *reinterpret_cast<uint4*>(&V_lds[row * VS + colc]) = vs[0];
+    *reinterpret_cast<uint4*>(&V_lds[row * VS + colc + 8]) = vs[1];
+  } else {
+    uint4 zero{0, 0, 0, 0};
+    *reinterpret_cast<uint4*>(&K_lds[row * KS + colc]) = zero;
+    *reinterpret_cast<uint4*>(&K_lds[row * KS + colc + 8]) = zero;
+    *reinterpret_cast<uint4*>(&V_lds[row * VS + colc]) = zero;
+    *reinterpret_cast<uint4*>(&V_lds[row * VS + colc + 8]) = zero;
+  }
+}
+
+// Stage the keep-mask words of q-rows q0..q0+127 for key tile k0 as
+// [128 q][2 words] (k0 is a multiple of 64, so two words cover its 64
+// keys), one word per thread; all-ones past the sequence or the row.
+__device__ __forceinline__ void stage_mask_words(uint32_t* mk_lds,
+                                                 const uint32_t* mask_base,
+                                                 int q0, int k0, int L,
+                                                 int Sw, int tid) {
+  const int qrow_m = q0 + (tid >> 1);
+  const int kw = (k0 >> 5) + (tid & 1);
+  uint32_t bits = 0xFFFFFFFFu;
+  if (qrow_m < L && kw < Sw)
+    bits = mask_base[static_cast<int64_t>(qrow_m) * Sw + kw];
+  mk_lds[tid] = bits;
+}
+
 // ---------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------
@@ -190,10 +246,11 @@ template <typename T, bool TRAIN_DROP, bool VARLEN = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(
     const T* __restrict__ qkv, const int* __restrict__ seqlens,
     T* __restrict__ out, float* __restrict__ lse_out,
-    const uint32_t* __restrict__ dmask, int B, int S, int NH, float p,
-    float scale, uint64_t seed, uint64_t offset) {
+    const uint32_t* __restrict__ dmask, int S, int NH, float p,
+    float scale) {
   using Tr = Mfma16<T>;
   using F8 = typename Tr::frag;
+  using Lds = AttnFwdLds<T>;
   // 4 waves x 32 q-rows (two 16-row subtiles per wave): the K/V tile is
   // staged once per 128 q-rows, each K/V fragment read feeds TWO
   // independent MFMA chains, and the softmax work of the two subtiles
@@ -206,6 +263,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   const int g = (lane >> 4), li = lane & 15;
   const int H = NH * 64;
   const int rs3 = 3 * H;  // qkv row stride
+  // (this sequence prologue is repeated in attn_dq_kernel and
+  // attn_bwd_kernel: a shared struct spilled in attn_bwd_kernel, see
+  // profiles/attention_refactor.md)
   const int64_t row0 = seq_row0<VARLEN>(seqlens, b, S);
   const int L = seq_rows<VARLEN>(seqlens, b, S);  // row bound of this sequence
   const T* qbase = qkv + row0 * rs3 + h * 64;
@@ -221,14 +281,13 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   if (VARLEN && q0 >= L) return;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* K_lds = reinterpret_cast<T*>(smem);             // [64][72]
-  T* V_lds = K_lds + 64 * kStride;   // [64][80] natural, tr-read
-  float* alpha_lds = reinterpret_cast<float*>(V_lds + 64 * kTrStride);  // [4][2][16]
-  float* stat_lds = alpha_lds + 4 * 2 * 16;                    // [4][2][16]
-  // keep-mask words for the current kv-tile, [128 q][2 words]: staged
-  // coalesced (one word per thread) instead of per-lane scattered 4-byte
-  // global reads in the softmax loop
-  uint32_t* mk_lds = reinterpret_cast<uint32_t*>(stat_lds + 4 * 2 * 16);
+  T* K_lds = lds_at<T>(smem, Lds::k);
+  T* V_lds = lds_at<T>(smem, Lds::v);
+  float* alpha_lds = lds_at<float>(smem, Lds::alpha);
+  float* stat_lds = lds_at<float>(smem, Lds::stat);
+  // keep-mask words are staged coalesced (one word per thread) instead
+  // of per-lane scattered 4-byte global reads in the softmax loop
+  uint32_t* mk_lds = lds_at<uint32_t>(smem, Lds::mask);
 
   // this wave's two q-subtiles: rows q0 + wave*32 + sub*16 + li
   int q_row[2];
@@ -250,35 +309,9 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
   for (int kt = 0; kt < n_kv; ++kt) {
     const int k0 = kt * 64;
     __syncthreads();
-    // stage K natural + V transposed; 4 threads per row, 16 cols each
-    {
-      const int row = tid >> 2, colc = (tid & 3) * 16;
-      const int krow = k0 + row;
-      if (krow < L) {
-        const uint4* src =
-            reinterpret_cast<const uint4*>(kbase + static_cast<int64_t>(krow) * rs3 + colc);
-        *reinterpret_cast<uint4*>(&K_lds[row * kStride + colc]) = src[0];
-        *reinterpret_cast<uint4*>(&K_lds[row * kStride + colc + 8]) = src[1];
-        const uint4* vsrc =
-            reinterpret_cast<const uint4*>(vbase + static_cast<int64_t>(krow) * rs3 + colc);
-        *reinterpret_cast<uint4*>(&V_lds[row * kTrStride + colc]) = vsrc[0];
-        *reinterpret_cast<uint4*>(&V_lds[row * kTrStride + colc + 8]) = vsrc[1];
-      } else {
-        uint4 zero{0, 0, 0, 0};
-        *reinterpret_cast<uint4*>(&K_lds[row * kStride + colc]) = zero;
-        *reinterpret_cast<uint4*>(&K_lds[row * kStride + colc + 8]) = zero;
-        *reinterpret_cast<uint4*>(&V_lds[row * kTrStride + colc]) = zero;
-        *reinterpret_cast<uint4*>(&V_lds[row * kTrStride + colc + 8]) = zero;
-      }
-      if (TRAIN_DROP) {
-        const int qrow_m = q0 + (tid >> 1);
-        const int kw = (k0 >> 5) + (tid & 1);  // 2 words cover 64 keys
-        uint32_t bits = 0xFFFFFFFFu;
-        if (qrow_m < L && kw < Sw)
-          bits = mask_base[static_cast<int64_t>(qrow_m) * Sw + kw];
-        mk_lds[tid] = bits;
-      }
-    }
+    stage_kv_tile<kStride, kTrStride>(K_lds, V_lds, kbase, vbase, k0, L, rs3,
+                                      tid);
+    if (TRAIN_DROP) stage_mask_words(mk_lds, mask_base, q0, k0, L, Sw, tid);
     __syncthreads();
 
     // S^T tiles: one K-fragment pair feeds both subtiles' MFMA chains
@@ -368,10 +401,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        union {
-          F8 v;
-          T e[8];
-        } pk;
+        FragBits<T> pk;
 #pragma unroll
         for (int e = 0; e < 8; ++e)
           pk.e[e] = Tr::from_f32(sv[sub][2 * c + (e >> 2)][e & 3]);
@@ -381,8 +411,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-      const F8 vf0 = frag_tr(V_lds, 0, n * 16);
-      const F8 vf1 = frag_tr(V_lds, 32, n * 16);
+      const F8 vf0 = frag_tr<kTrStride>(V_lds, 0, n * 16);
+      const F8 vf1 = frag_tr<kTrStride>(V_lds, 32, n * 16);
       acc_o[0][n] = Tr::mfma(pa[0][0], vf0, acc_o[0][n]);
       acc_o[1][n] = Tr::mfma(pa[1][0], vf0, acc_o[1][n]);
       acc_o[0][n] = Tr::mfma(pa[0][1], vf1, acc_o[0][n]);
@@ -426,11 +456,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(
 // touch 128 contiguous bytes), and the row sum needs only 3 xor-shuffle
 // rounds within the 8-lane group (the old wave-per-row version was
 // reduce-latency-bound at 0.17 TB/s).
-template <typename T>
-__global__ void attn_delta_kernel(const T* __restrict__ dout,
-                                  const T* __restrict__ out,
-                                  float* __restrict__ delta, int B, int S,
-                                  int NH) {
+// In the packed layout the dO/O row is found through cu_seqlens; slots
+// past a sequence's length have no dO/O row, are skipped (the 8 lanes
+// of a row leave together) and are never read by the backward kernels.
+template <typename T, bool VARLEN>
+__device__ __forceinline__ void attn_delta_rows(
+    const T* __restrict__ dout, const T* __restrict__ out,
+    float* __restrict__ delta, const int* __restrict__ cu_seqlens, int B,
+    int S, int NH) {
   const int H = NH * 64;
   const int64_t rows = static_cast<int64_t>(B) * NH * S;
   const int lane = threadIdx.x & 63;
@@ -443,8 +476,9 @@ __global__ void attn_delta_kernel(const T* __restrict__ dout,
   const int64_t bh = row / S;
   const int q = static_cast<int>(row % S);
   const int b = static_cast<int>(bh) / NH, h = static_cast<int>(bh) % NH;
+  if (VARLEN && q >= seq_rows<VARLEN>(cu_seqlens, b, S)) return;
   const int64_t base =
-      (static_cast<int64_t>(b) * S + q) * H + h * 64 + part * 8;
+      (seq_row0<VARLEN>(cu_seqlens, b, S) + q) * H + h * 64 + part * 8;
   using Tr = Mfma16<T>;
   T dv[8], ov[8];
   *reinterpret_cast<uint4*>(dv) = *reinterpret_cast<const uint4*>(dout + base);
@@ -457,43 +491,24 @@ __global__ void attn_delta_kernel(const T* __restrict__ dout,
   if (part == 0) delta[row] = acc;
 }
 
-// Packed-layout delta: the same lane mapping and the same [B*NH, S]
-// delta rows, with the dO/O row found through cu_seqlens. Slots past a
-// sequence's length have no dO/O row; they are skipped (the 8 lanes of
-// a row leave together) and never read by the backward kernels. A
-// kernel of its own so that the padded kernel above stays byte-for-byte
-// what it was.
+// Two thin kernels over the one body rather than a VARLEN parameter on
+// one kernel: the padded kernel's argument block has no cu_seqlens
+// pointer, and stays as it is.
+template <typename T>
+__global__ void attn_delta_kernel(const T* __restrict__ dout,
+                                  const T* __restrict__ out,
+                                  float* __restrict__ delta, int B, int S,
+                                  int NH) {
+  attn_delta_rows<T, false>(dout, out, delta, nullptr, B, S, NH);
+}
+
 template <typename T>
 __global__ void attn_delta_varlen_kernel(const T* __restrict__ dout,
                                          const T* __restrict__ out,
                                          float* __restrict__ delta,
                                          const int* __restrict__ cu_seqlens,
                                          int B, int S, int NH) {
-  const int H = NH * 64;
-  const int64_t rows = static_cast<int64_t>(B) * NH * S;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int sub = lane >> 3;
-  const int part = lane & 7;
-  const int64_t row =
-      (static_cast<int64_t>(blockIdx.x) * (blockDim.x >> 6) + wave) * 8 + sub;
-  if (row >= rows) return;
-  const int64_t bh = row / S;
-  const int q = static_cast<int>(row % S);
-  const int b = static_cast<int>(bh) / NH, h = static_cast<int>(bh) % NH;
-  if (q >= seq_rows<true>(cu_seqlens, b, S)) return;
-  const int64_t base =
-      (seq_row0<true>(cu_seqlens, b, S) + q) * H + h * 64 + part * 8;
-  using Tr = Mfma16<T>;
-  T dv[8], ov[8];
-  *reinterpret_cast<uint4*>(dv) = *reinterpret_cast<const uint4*>(dout + base);
-  *reinterpret_cast<uint4*>(ov) = *reinterpret_cast<const uint4*>(out + base);
-  float acc = 0.f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) acc += Tr::to_f32(dv[k]) * Tr::to_f32(ov[k]);
-#pragma unroll
-  for (int off = 4; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE_SIZE);
-  if (part == 0) delta[row] = acc;
+  attn_delta_rows<T, true>(dout, out, delta, cu_seqlens, B, S, NH);
 }
 
 // dQ kernel: wave-owns-q structure copied from attn_fwd_kernel.
@@ -507,10 +522,10 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
     const T* __restrict__ dout, const T* __restrict__ qkv,
     const int* __restrict__ seqlens, const float* __restrict__ lse,
     const float* __restrict__ delta, const uint32_t* __restrict__ dmask,
-    T* __restrict__ dqkv, int B, int S, int NH, float p, float scale,
-    uint64_t seed, uint64_t offset) {
+    T* __restrict__ dqkv, int S, int NH, float p, float scale) {
   using Tr = Mfma16<T>;
   using F8 = typename Tr::frag;
+  using Lds = AttnDqLds<T>;
   // 4 waves x 32 q-rows (two 16-row subtiles per wave), mirroring
   // attn_fwd_kernel: K/V/K^T staged once per 128 q-rows, every staged
   // fragment feeds two independent MFMA chains.
@@ -540,9 +555,9 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
   // K natural at kTrStride: serves BOTH the S^T-recompute row fragments
   // (2-way bank conflicts, tolerated) and the dQ chain's K^T fragments
   // via hardware transpose reads - no separate transposed image.
-  T* K_lds = reinterpret_cast<T*>(smem);   // [64][80] natural
-  T* V_lds = K_lds + 64 * kTrStride;            // [64][72] natural
-  uint32_t* mk_lds = reinterpret_cast<uint32_t*>(V_lds + 64 * kStride);
+  T* K_lds = lds_at<T>(smem, Lds::k);
+  T* V_lds = lds_at<T>(smem, Lds::v);
+  uint32_t* mk_lds = lds_at<uint32_t>(smem, Lds::mask);
 
   // this wave's two q-subtiles: Q/dO fragments + lse/delta in registers
   int q_row[2];
@@ -571,44 +586,15 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
   for (int kt = 0; kt < n_kv; ++kt) {
     const int k0 = kt * 64;
     __syncthreads();
-    {
-      const int row = tid >> 2, colc = (tid & 3) * 16;
-      const int krow = k0 + row;
-      if (krow < L) {
-        const uint4* ks = reinterpret_cast<const uint4*>(
-            kbase + static_cast<int64_t>(krow) * rs3 + colc);
-        *reinterpret_cast<uint4*>(&K_lds[row * kTrStride + colc]) = ks[0];
-        *reinterpret_cast<uint4*>(&K_lds[row * kTrStride + colc + 8]) = ks[1];
-        const uint4* vs = reinterpret_cast<const uint4*>(
-            vbase + static_cast<int64_t>(krow) * rs3 + colc);
-        *reinterpret_cast<uint4*>(&V_lds[row * kStride + colc]) = vs[0];
-        *reinterpret_cast<uint4*>(&V_lds[row * kStride + colc + 8]) = vs[1];
-      } else {
-        uint4 zero{0, 0, 0, 0};
-        *reinterpret_cast<uint4*>(&K_lds[row * kTrStride + colc]) = zero;
-        *reinterpret_cast<uint4*>(&K_lds[row * kTrStride + colc + 8]) = zero;
-        *reinterpret_cast<uint4*>(&V_lds[row * kStride + colc]) = zero;
-        *reinterpret_cast<uint4*>(&V_lds[row * kStride + colc + 8]) = zero;
-      }
-      if (TRAIN_DROP) {
-        const int qrow_m = q0 + (tid >> 1);
-        const int kw = (k0 >> 5) + (tid & 1);
-        uint32_t bits = 0xFFFFFFFFu;
-        if (qrow_m < L && kw < Sw)
-          bits = mask_base[static_cast<int64_t>(qrow_m) * Sw + kw];
-        mk_lds[tid] = bits;
-      }
-    }
+    stage_kv_tile<kTrStride, kStride>(K_lds, V_lds, kbase, vbase, k0, L, rs3,
+                                      tid);
+    if (TRAIN_DROP) stage_mask_words(mk_lds, mask_base, q0, k0, L, Sw, tid);
     __syncthreads();
 
     // S^T and dP^T tiles (C[key][q], q = li); K/V fragments shared.
     // dS packs straight into its A-fragment slots (element
     // e = (t&1)*4 + r of chunk t>>1) - no [2][4][4] staging array.
-    union FB {
-      F8 v;
-      T e[8];
-    };
-    FB dsfrag[2][2];
+    FragBits<T> dsfrag[2][2];
     // (setprio brackets are inside the loops below)
     // keep-mask words for this kv-tile (two words cover keys
     // k0..k0+63 for each q-subtile; k0 is a multiple of 64)
@@ -658,8 +644,8 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
-      const F8 ktf0 = frag_tr(K_lds, 0, n * 16);
-      const F8 ktf1 = frag_tr(K_lds, 32, n * 16);
+      const F8 ktf0 = frag_tr<kTrStride>(K_lds, 0, n * 16);
+      const F8 ktf1 = frag_tr<kTrStride>(K_lds, 32, n * 16);
       acc_dq[0][n] = Tr::mfma(dsfrag[0][0].v, ktf0, acc_dq[0][n]);
       acc_dq[1][n] = Tr::mfma(dsfrag[1][0].v, ktf0, acc_dq[1][n]);
       acc_dq[0][n] = Tr::mfma(dsfrag[0][1].v, ktf1, acc_dq[0][n]);
@@ -690,10 +676,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     const T* __restrict__ dout, const T* __restrict__ qkv,
     const int* __restrict__ seqlens, const float* __restrict__ lse,
     const float* __restrict__ delta, const uint32_t* __restrict__ dmask,
-    T* __restrict__ dqkv, int B, int S, int NH, float p, float scale,
-    uint64_t seed, uint64_t offset) {
+    T* __restrict__ dqkv, int S, int NH, float p, float scale) {
   using Tr = Mfma16<T>;
   using F8 = typename Tr::frag;
+  using Lds = AttnBwdLds<T>;
   // 4 waves x 32 keys (two 16-key subtiles per wave): the heavy per-
   // q-tile staging of Q/Q^T/dO/dO^T is amortized over 128 keys, and
   // every staged Q/dO/Q^T/dO^T fragment feeds two MFMA chains.
@@ -724,18 +710,20 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
   // 2-way conflicts) and the dK/dV chains' transposed fragments via
   // hardware transpose reads - the Qt/dOt images and their 16-scalar-
   // write-per-thread transpose scatters are gone.
-  T* K_lds = reinterpret_cast<T*>(smem);   // [128][72] natural
-  T* V_lds = K_lds + 128 * kStride;             // [128][72] natural
-  T* Q_lds = V_lds + 128 * kStride;             // [64][80] natural
-  T* dO_lds = Q_lds + 64 * kTrStride;           // [64][80] natural
-  float* lse_lds = reinterpret_cast<float*>(dO_lds + 64 * kTrStride);  // [64]
-  float* dlt_lds = lse_lds + 64;                                      // [64]
-  // keep-mask tile [64 q][128 keys] as bits, [4 words][64 q], staged per
-  // q-tile (raw global reads were byte columns - latency-bound at this
-  // kernel's occupancy; 16 lanes share each word via LDS broadcast)
-  uint32_t* mk_lds = reinterpret_cast<uint32_t*>(dlt_lds + 64);
+  T* K_lds = lds_at<T>(smem, Lds::k);
+  T* V_lds = lds_at<T>(smem, Lds::v);
+  T* Q_lds = lds_at<T>(smem, Lds::q);
+  T* dO_lds = lds_at<T>(smem, Lds::d_o);
+  float* lse_lds = lds_at<float>(smem, Lds::lse);
+  float* dlt_lds = lds_at<float>(smem, Lds::delta);
+  // keep-mask tile staged per q-tile (raw global reads were byte
+  // columns - latency-bound at this kernel's occupancy; 16 lanes share
+  // each word via LDS broadcast)
+  uint32_t* mk_lds = lds_at<uint32_t>(smem, Lds::mask);
 
   // stage K and V (natural) once: two 64-row passes
+  // (not stage_kv_tile, whose store-in-each-branch form compiles to
+  // other code here: see profiles/attention_refactor.md)
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
     const int row = pass * 64 + (tid >> 2), colc = (tid & 3) * 16;
@@ -835,11 +823,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     // is produced (element e = (mq&1)*4 + r of chunk mq>>1) - no
     // [2][4][4] staging arrays (they cost ~64 VGPRs and halved
     // occupancy at 324 VGPRs/wave)
-    union FB {
-      F8 v;
-      T e[8];
-    };
-    FB pfrag[2][2], dsfrag[2][2];
+    FragBits<T> pfrag[2][2], dsfrag[2][2];
 #pragma unroll
     for (int mq = 0; mq < 4; ++mq) {
       const T* qrow_n = &Q_lds[(mq * 16 + li) * kTrStride];
@@ -892,10 +876,10 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-      const F8 dt0 = frag_tr(dO_lds, 0, m * 16);
-      const F8 dt1 = frag_tr(dO_lds, 32, m * 16);
-      const F8 qt0 = frag_tr(Q_lds, 0, m * 16);
-      const F8 qt1 = frag_tr(Q_lds, 32, m * 16);
+      const F8 dt0 = frag_tr<kTrStride>(dO_lds, 0, m * 16);
+      const F8 dt1 = frag_tr<kTrStride>(dO_lds, 32, m * 16);
+      const F8 qt0 = frag_tr<kTrStride>(Q_lds, 0, m * 16);
+      const F8 qt1 = frag_tr<kTrStride>(Q_lds, 32, m * 16);
       dv_acc[0][m] = Tr::mfma(dt0, pfrag[0][0].v, dv_acc[0][m]);
       dv_acc[1][m] = Tr::mfma(dt0, pfrag[1][0].v, dv_acc[1][m]);
       dv_acc[0][m] = Tr::mfma(dt1, pfrag[0][1].v, dv_acc[0][m]);
@@ -928,210 +912,252 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// ds_read_b64_tr_b16 semantics probe (debug utility; used once per ROCm
-// bump to verify the lane->element mapping the PV/dK/dV fragment reads
-// rely on). LDS is filled with the identity pattern (element i = i) and
-// each lane reads at its own 8-byte-aligned address (8*lane bytes);
-// out[l][j] then IS the element index lane l's slot j received.
+// launch path, shared by the padded and the packed layout
 // ---------------------------------------------------------------------------
-__global__ void tr16_probe_kernel(float* __restrict__ out, int addr_mode) {
-  __shared__ __bf16 lds[1024];
-  const int t = threadIdx.x;
-  for (int i = t; i < 1024; i += 64) lds[i] = __bf16(static_cast<float>(i));
-  __syncthreads();
-  typedef __attribute__((__vector_size__(4 * sizeof(__bf16)))) __bf16 bf16x4v;
-  int elem_off;
-  switch (addr_mode) {
-    case 0: elem_off = t * 4; break;           // 8 B per lane, contiguous
-    case 1: elem_off = 0; break;               // uniform base
-    case 2: elem_off = (t & 15) * 4; break;    // repeats per 16-lane group
-    default: elem_off = (t >> 4) * 4; break;   // group-constant
-  }
-  auto p = (__attribute__((address_space(3))) bf16x4v*)(&lds[elem_off]);
-  bf16x4v v = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(p);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) out[t * 4 + j] = static_cast<float>(v[j]);
-}
+// One attention call. `seq` is seqlens[B] in the padded layout and
+// cu_seqlens[B+1] in the packed one; S is the padded or the maximal
+// sequence length. lse, delta and the keep-mask are [B*NH, S, ..] in both.
+struct AttnShape {
+  const int* seq;
+  int B, S, NH;
+};
 
-torch::Tensor tr16_probe(int64_t addr_mode) {
-  auto out = torch::empty({64, 4}, torch::TensorOptions()
-                                       .dtype(torch::kFloat32)
-                                       .device(torch::kCUDA));
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(tr16_probe_kernel, dim3(1), dim3(64), 0, stream,
-                     out.data_ptr<float>(), static_cast<int>(addr_mode));
-  return out;
-}
-
-// ---------------------------------------------------------------------------
-// host wrappers
-// ---------------------------------------------------------------------------
-template <typename T>
-static std::vector<torch::Tensor> attention_fwd_t(torch::Tensor qkv,
-                                                  torch::Tensor seqlens,
-                                                  int64_t num_heads, double p,
-                                                  int64_t seed,
-                                                  int64_t offset) {
-  const int B = qkv.size(0), S = qkv.size(1);
-  const int H = qkv.size(2) / 3;
-  const int NH = static_cast<int>(num_heads);
-  TORCH_CHECK(H == NH * 64, "attn_fwd: head_dim must be 64");
-  TORCH_CHECK(S % 16 == 0, "attn_fwd: S must be a multiple of 16");
-  auto seql = seqlens.to(qkv.device(), torch::kInt32).contiguous();
-  auto out = torch::empty({B, S, H}, qkv.options());
-  auto lse = torch::empty({B * NH, S}, qkv.options().dtype(torch::kFloat32));
+// Allocates lse and the keep-mask, generates the mask and runs the
+// forward into `out` (allocated by the caller in its layout).
+template <typename T, bool VARLEN>
+static std::vector<torch::Tensor> attn_launch_fwd(
+    const AttnShape& a, const torch::Tensor& qkv, torch::Tensor out, double p,
+    int64_t seed, int64_t offset) {
+  const int B = a.B, S = a.S, NH = a.NH;
+  const int64_t heads = static_cast<int64_t>(B) * NH;
+  auto lse = torch::empty({heads, S}, qkv.options().dtype(torch::kFloat32));
   const bool train_drop = p > 0.0;
   // keep-mask BITS [B*NH, S, ceil(S/32)] int32 words: written once
   // here, read (not regenerated) by both backward kernels
   const int Sw = (S + 31) / 32;
-  auto dmask = train_drop
-                   ? torch::empty({static_cast<int64_t>(B) * NH, S, Sw},
-                                  qkv.options().dtype(torch::kInt32))
-                   : torch::empty({0}, qkv.options().dtype(torch::kInt32));
-  const float scale = 1.0f / sqrtf(64.f);
+  auto dmask = train_drop ? torch::empty({heads, S, Sw},
+                                         qkv.options().dtype(torch::kInt32))
+                          : torch::empty({0}, qkv.options().dtype(torch::kInt32));
+  if (B == 0) return {out, lse, dmask};  // a packed batch of no sequences
   auto stream = at::hip::getCurrentHIPStream();
-  dim3 grid((S + 127) / 128, B * NH), block(256);  // 128 q-rows per block
-  const size_t lds = (64 * kStride + 64 * kTrStride) * sizeof(T) +
-                     4 * 64 * sizeof(float) + 128 * 2 * sizeof(uint32_t);
+  float p_q = 0.f;
   if (train_drop) {
-    const auto [thresh, p_q] = quantize_drop_p(p);
-    const int64_t words = static_cast<int64_t>(B) * NH * S * Sw;
+    const auto quant = quantize_drop_p(p);
+    p_q = quant.second;
+    const int64_t words = heads * S * Sw;
     hipLaunchKernelGGL(dropout_mask_kernel,
                        dim3((words + 255) / 256), dim3(256), 0, stream,
                        reinterpret_cast<uint32_t*>(dmask.data_ptr<int>()),
-                       words, thresh, static_cast<uint64_t>(seed),
-                       static_cast<uint64_t>(offset));
-    hipLaunchKernelGGL((attn_fwd_kernel<T, true>), grid, block, lds, stream,
-                       reinterpret_cast<const T*>(qkv.data_ptr()),
-                       seql.data_ptr<int>(),
-                       reinterpret_cast<T*>(out.data_ptr()),
-                       lse.data_ptr<float>(),
-                       reinterpret_cast<const uint32_t*>(
-                           dmask.data_ptr<int>()),
-                       B, S, NH, p_q, scale,
-                       static_cast<uint64_t>(seed),
-                       static_cast<uint64_t>(offset));
-  } else {
-    hipLaunchKernelGGL((attn_fwd_kernel<T, false>), grid, block, lds, stream,
-                       reinterpret_cast<const T*>(qkv.data_ptr()),
-                       seql.data_ptr<int>(),
-                       reinterpret_cast<T*>(out.data_ptr()),
-                       lse.data_ptr<float>(), nullptr, B, S, NH,
-                       static_cast<float>(p), scale,
-                       static_cast<uint64_t>(seed),
+                       words, quant.first, static_cast<uint64_t>(seed),
                        static_cast<uint64_t>(offset));
   }
+  const float scale = 1.0f / sqrtf(64.f);
+  const dim3 grid((S + 127) / 128, B * NH), block(256);  // 128 q-rows per block
+  auto launch = [&](auto drop) {
+    constexpr bool kDrop = decltype(drop)::value;
+    hipLaunchKernelGGL(
+        (attn_fwd_kernel<T, kDrop, VARLEN>), grid, block,
+        AttnFwdLds<T>::bytes, stream,
+        reinterpret_cast<const T*>(qkv.data_ptr()), a.seq,
+        reinterpret_cast<T*>(out.data_ptr()), lse.data_ptr<float>(),
+        kDrop ? reinterpret_cast<const uint32_t*>(dmask.data_ptr<int>())
+              : nullptr,
+        S, NH, p_q, scale);
+  };
+  if (train_drop)
+    launch(std::true_type{});
+  else
+    launch(std::false_type{});
   return {out, lse, dmask};
 }
 
+// delta, then dK/dV (attn_bwd_kernel) and dQ (attn_dq_kernel) into
+// `dqkv` (allocated by the caller in its layout).
+template <typename T, bool VARLEN>
+static void attn_launch_bwd(const AttnShape& a, const torch::Tensor& dout,
+                            const torch::Tensor& qkv,
+                            const torch::Tensor& out,
+                            const torch::Tensor& lse,
+                            const torch::Tensor& dmask, torch::Tensor& dqkv,
+                            double p) {
+  const int B = a.B, S = a.S, NH = a.NH;
+  if (B == 0) return;
+  auto stream = at::hip::getCurrentHIPStream();
+  auto dout_c = dout.contiguous();
+  const T* dout_p = reinterpret_cast<const T*>(dout_c.data_ptr());
+  const T* out_p = reinterpret_cast<const T*>(out.data_ptr());
+  const int64_t rows = static_cast<int64_t>(B) * NH * S;
+  auto delta = torch::empty({rows}, qkv.options().dtype(torch::kFloat32));
+
+  const int64_t delta_waves = (rows + 7) / 8;  // 8 rows per wave
+  const dim3 delta_grid((delta_waves + 3) / 4), block(256);
+  if constexpr (VARLEN)
+    hipLaunchKernelGGL(attn_delta_varlen_kernel<T>, delta_grid, block, 0,
+                       stream, dout_p, out_p, delta.data_ptr<float>(), a.seq,
+                       B, S, NH);
+  else
+    hipLaunchKernelGGL(attn_delta_kernel<T>, delta_grid, block, 0, stream,
+                       dout_p, out_p, delta.data_ptr<float>(), B, S, NH);
+
+  // 128 keys per bwd block, 128 q-rows per dq block
+  const dim3 grid((S + 127) / 128, B * NH);
+  const float scale = 1.0f / sqrtf(64.f);
+  const bool train_drop = p > 0.0;
+  // same 8-bit quantization as the forward's mask generation, so the
+  // backward keep-scale matches the stored mask's statistics exactly
+  const float p_q = train_drop ? quantize_drop_p(p).second : 0.f;
+  const uint32_t* mask_p =
+      train_drop ? reinterpret_cast<const uint32_t*>(dmask.data_ptr<int>())
+                 : nullptr;
+  auto launch = [&](auto kernel, size_t lds_bytes) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, dout_p,
+                       reinterpret_cast<const T*>(qkv.data_ptr()), a.seq,
+                       lse.data_ptr<float>(), delta.data_ptr<float>(), mask_p,
+                       reinterpret_cast<T*>(dqkv.data_ptr()), S, NH, p_q,
+                       scale);
+  };
+  auto launch_both = [&](auto drop) {
+    constexpr bool kDrop = decltype(drop)::value;
+    HIP_CHECK(hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&attn_bwd_kernel<T, kDrop, VARLEN>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, AttnBwdLds<T>::bytes));
+    launch(&attn_bwd_kernel<T, kDrop, VARLEN>, AttnBwdLds<T>::bytes);
+    launch(&attn_dq_kernel<T, kDrop, VARLEN>, AttnDqLds<T>::bytes);
+  };
+  if (train_drop)
+    launch_both(std::true_type{});
+  else
+    launch_both(std::false_type{});
+}
+
+// ---------------------------------------------------------------------------
+// operand checks and dtype dispatch of the entry points
+// ---------------------------------------------------------------------------
+static void check_elem_dtype(const char* who, const torch::Tensor& qkv) {
+  const auto dt = qkv.scalar_type();
+  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf, who,
+              ": qkv must be bf16 or fp16, got ", dt);
+}
+
+template <typename T>
+struct ElemTag {
+  using type = T;
+};
+
+// f(ElemTag<T>{}) with T the 16-bit element type of qkv (checked before)
+template <typename F>
+static auto dispatch_elem(const torch::Tensor& qkv, F&& f) {
+  if (qkv.scalar_type() == torch::kHalf) return f(ElemTag<_Float16>{});
+  return f(ElemTag<__bf16>{});
+}
+
+static void check_padded_args(const torch::Tensor& qkv,
+                              const torch::Tensor& seqlens,
+                              int64_t num_heads, const char* who) {
+  check_elem_dtype(who, qkv);
+  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(), who,
+              ": qkv must be a contiguous [B, S, 3H] tensor");
+  TORCH_CHECK(qkv.size(2) == 3 * num_heads * 64, who,
+              ": head_dim must be 64");
+  TORCH_CHECK(qkv.size(1) % 16 == 0, who, ": S must be a multiple of 16");
+  TORCH_CHECK(seqlens.numel() == qkv.size(0), who, ": seqlens must have B = ",
+              qkv.size(0), " entries, got ", seqlens.numel());
+  TORCH_CHECK(qkv.size(0) * num_heads <= 65535, who,
+              ": B * num_heads exceeds the grid's y limit");
+}
+
+static void check_varlen_args(const torch::Tensor& qkv,
+                              const torch::Tensor& cu_seqlens,
+                              int64_t max_seqlen, int64_t num_heads,
+                              const char* who) {
+  check_elem_dtype(who, qkv);
+  TORCH_CHECK(qkv.dim() == 2 && qkv.is_contiguous(), who,
+              ": qkv must be a contiguous [T_pad, 3H] matrix");
+  TORCH_CHECK(qkv.size(1) == 3 * num_heads * 64, who,
+              ": head_dim must be 64");
+  TORCH_CHECK(cu_seqlens.dim() == 1 && cu_seqlens.size(0) >= 1 &&
+                  cu_seqlens.scalar_type() == torch::kInt32 &&
+                  cu_seqlens.is_contiguous() &&
+                  cu_seqlens.device() == qkv.device(),
+              who, ": cu_seqlens must be a contiguous int32 [B+1] tensor "
+                   "on qkv's device");
+  TORCH_CHECK(max_seqlen >= 1, who, ": max_seqlen must be positive");
+  TORCH_CHECK((cu_seqlens.size(0) - 1) * num_heads <= 65535, who,
+              ": B * num_heads exceeds the grid's y limit");
+}
+
+// The backward kernels reinterpret dout/out as qkv's dtype and index
+// them, lse and the keep-mask by qkv's shape: dout and out are qkv's
+// shape with H for 3H, lse is [heads, S] fp32, the mask [heads, S,
+// ceil(S/32)] int32 (read only with p > 0), heads = B*NH.
+static void check_bwd_operands(const char* who, const torch::Tensor& dout,
+                               const torch::Tensor& qkv,
+                               const torch::Tensor& out,
+                               const torch::Tensor& lse,
+                               const torch::Tensor& dmask, int64_t heads,
+                               int64_t S, double p) {
+  const auto dt = qkv.scalar_type();
+  TORCH_CHECK(dout.scalar_type() == dt, who, ": dout dtype ",
+              dout.scalar_type(), " does not match qkv dtype ", dt);
+  TORCH_CHECK(out.scalar_type() == dt, who, ": out dtype ",
+              out.scalar_type(), " does not match qkv dtype ", dt);
+  auto shape = qkv.sizes().vec();
+  shape.back() /= 3;
+  const at::IntArrayRef want(shape);
+  TORCH_CHECK(dout.sizes() == want, who, ": dout shape ", dout.sizes(),
+              " must be ", want);
+  TORCH_CHECK(out.sizes() == want, who, ": out shape ", out.sizes(),
+              " must be ", want);
+  TORCH_CHECK(out.is_contiguous(), who, ": out must be contiguous");
+  check_row_stat(who, "lse", lse, heads * S);
+  if (p > 0.0) check_bit_mask(who, dmask, heads, S);
+}
+
+// ---------------------------------------------------------------------------
+// padded entry points
+// ---------------------------------------------------------------------------
 // qkv [B,S,3H] bf16 or fp16 -> {out [B,S,H] same dtype, lse fp32, keep-mask}
 std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
                                          torch::Tensor seqlens,
                                          int64_t num_heads, double p,
                                          int64_t seed, int64_t offset) {
-  TORCH_CHECK(qkv.dim() == 3 && qkv.is_contiguous(), "attn_fwd: bad qkv");
-  const auto dt = qkv.scalar_type();
-  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
-              "attn_fwd: qkv must be bf16 or fp16, got ", dt);
-  if (dt == torch::kHalf)
-    return attention_fwd_t<_Float16>(qkv, seqlens, num_heads, p, seed,
-                                     offset);
-  return attention_fwd_t<__bf16>(qkv, seqlens, num_heads, p, seed, offset);
-}
-
-template <typename T>
-static torch::Tensor attention_bwd_t(torch::Tensor dout, torch::Tensor qkv,
-                                     torch::Tensor seqlens, torch::Tensor out,
-                                     torch::Tensor lse, torch::Tensor dmask,
-                                     int64_t num_heads, double p,
-                                     int64_t seed, int64_t offset) {
+  check_padded_args(qkv, seqlens, num_heads, "attn_fwd");
   const int B = qkv.size(0), S = qkv.size(1);
-  const int H = qkv.size(2) / 3;
   const int NH = static_cast<int>(num_heads);
   auto seql = seqlens.to(qkv.device(), torch::kInt32).contiguous();
-  auto dqkv = torch::empty_like(qkv);
-  auto fopts = qkv.options().dtype(torch::kFloat32);
-  auto delta = torch::empty({static_cast<int64_t>(B) * NH * S}, fopts);
-  auto stream = at::hip::getCurrentHIPStream();
-  auto dout_c = dout.contiguous();
-
-  const int64_t rows = static_cast<int64_t>(B) * NH * S;
-  const int64_t delta_waves = (rows + 7) / 8;  // 8 rows per wave
-  hipLaunchKernelGGL(attn_delta_kernel<T>, dim3((delta_waves + 3) / 4),
-                     dim3(256), 0, stream,
-                     reinterpret_cast<const T*>(dout_c.data_ptr()),
-                     reinterpret_cast<const T*>(out.data_ptr()),
-                     delta.data_ptr<float>(), B, S, NH);
-
-  dim3 grid((S + 127) / 128, B * NH), block(256);  // 128 keys per bwd block
-  dim3 grid_dq((S + 127) / 128, B * NH);           // 128 q-rows per dq block
-  // K/V hold 128 rows at kStride; Q/dO 64 rows at kTrStride (tr-read);
-  // + 1 KB bit-mask tile -> ~59 KB (over the 64 KB default dynamic-LDS
-  // cap; MI355X has 160 KB per CU)
-  const size_t lds = (4 * 64 * kStride + 2 * 64 * kTrStride) *
-                         sizeof(T) +
-                     2 * 64 * sizeof(float) + 64 * 4 * sizeof(uint32_t);
-  const size_t lds_dq = (64 * kStride + 64 * kTrStride) * sizeof(T) +
-                        128 * 2 * sizeof(uint32_t);
-  HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&attn_bwd_kernel<T, true>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&attn_bwd_kernel<T, false>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  const float scale = 1.0f / sqrtf(64.f);
-  const bool train_drop = p > 0.0;
-  // same 8-bit quantization as the forward's mask generation, so the
-  // backward keep-scale matches the stored mask's statistics exactly
-  const float p_q = quantize_drop_p(p).second;
-  const uint32_t* mask_ptr =
-      train_drop ? reinterpret_cast<const uint32_t*>(dmask.data_ptr<int>())
-                 : nullptr;
-  auto args = [&](auto kernel, dim3 g, size_t lds_bytes) {
-    hipLaunchKernelGGL(kernel, g, block, lds_bytes, stream,
-                       reinterpret_cast<const T*>(dout_c.data_ptr()),
-                       reinterpret_cast<const T*>(qkv.data_ptr()),
-                       seql.data_ptr<int>(), lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), mask_ptr,
-                       reinterpret_cast<T*>(dqkv.data_ptr()), B, S, NH,
-                       p_q, scale,
-                       static_cast<uint64_t>(seed),
-                       static_cast<uint64_t>(offset));
-  };
-  if (train_drop) {
-    args(attn_bwd_kernel<T, true>, grid, lds);
-    args(attn_dq_kernel<T, true>, grid_dq, lds_dq);
-  } else {
-    args(attn_bwd_kernel<T, false>, grid, lds);
-    args(attn_dq_kernel<T, false>, grid_dq, lds_dq);
-  }
-  return dqkv;
+  auto out = torch::empty({B, S, NH * 64}, qkv.options());
+  return dispatch_elem(qkv, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return attn_launch_fwd<T, false>({seql.data_ptr<int>(), B, S, NH}, qkv,
+                                     out, p, seed, offset);
+  });
 }
 
-// dout/qkv/out must share one dtype (bf16 or fp16); checked before any
-// launch so a mixed call cannot reinterpret one operand's bits.
+// All operands are checked for dtype, shape and contiguity before any
+// launch, so a malformed call cannot reinterpret or overrun one. seed
+// and offset are unused: the backward reads the stored keep-mask.
 torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
                             torch::Tensor seqlens, torch::Tensor out,
                             torch::Tensor lse, torch::Tensor dmask,
                             int64_t num_heads, double p, int64_t seed,
                             int64_t offset) {
-  const auto dt = qkv.scalar_type();
-  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
-              "attn_bwd: qkv must be bf16 or fp16, got ", dt);
-  TORCH_CHECK(dout.scalar_type() == dt,
-              "attn_bwd: dout dtype ", dout.scalar_type(),
-              " does not match qkv dtype ", dt);
-  TORCH_CHECK(out.scalar_type() == dt, "attn_bwd: out dtype ",
-              out.scalar_type(), " does not match qkv dtype ", dt);
-  if (dt == torch::kHalf)
-    return attention_bwd_t<_Float16>(dout, qkv, seqlens, out, lse, dmask,
-                                     num_heads, p, seed, offset);
-  return attention_bwd_t<__bf16>(dout, qkv, seqlens, out, lse, dmask,
-                                 num_heads, p, seed, offset);
+  check_padded_args(qkv, seqlens, num_heads, "attn_bwd");
+  const int B = qkv.size(0), S = qkv.size(1);
+  const int NH = static_cast<int>(num_heads);
+  check_bwd_operands("attn_bwd", dout, qkv, out, lse, dmask,
+                     static_cast<int64_t>(B) * NH, S, p);
+  auto seql = seqlens.to(qkv.device(), torch::kInt32).contiguous();
+  auto dqkv = torch::empty_like(qkv);
+  dispatch_elem(qkv, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    attn_launch_bwd<T, false>({seql.data_ptr<int>(), B, S, NH}, dout, qkv,
+                              out, lse, dmask, dqkv, p);
+  });
+  return dqkv;
 }
 
 // ---------------------------------------------------------------------------
-// variable-length (packed) host wrappers
+// variable-length (packed) entry points
 // ---------------------------------------------------------------------------
 // qkv is the packed [T_pad, 3H] QKV GEMM output of a batch whose valid
 // tokens sit back to back; cu_seqlens[B+1] int32 (device) is the
@@ -1139,8 +1165,8 @@ torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
 // and every length is <= max_seqlen. Neither is checked here (that
 // would be a device-to-host read); ops/varlen.py builds both from one
 // mask. lse and the keep-mask keep the padded kernel's layout with
-// S := max_seqlen, so dropout_mask_kernel is reused unchanged and the
-// mask equals the padded call's for the same (seed, offset, B, NH, S).
+// S := max_seqlen, so the mask equals the padded call's for the same
+// (seed, offset, B, NH, S).
 // Rows [T, T_pad) belong to no sequence: no attention block reads or
 // writes them, and zero_tail_rows_kernel sets them to zero in out /
 // dqkv (every row below T is written by exactly one attention block,
@@ -1165,90 +1191,16 @@ __global__ void zero_tail_rows_kernel(uint4* __restrict__ x,
     x[i] = uint4{0, 0, 0, 0};
 }
 
-static void zero_tail_rows(torch::Tensor& x, const torch::Tensor& cu_seqlens,
-                           hipStream_t stream) {
+static void zero_tail_rows(torch::Tensor& x, const torch::Tensor& cu_seqlens) {
+  if (x.size(0) == 0) return;
   // rows are 128 (out) or 384 (dqkv) bytes per head: whole 16 B chunks
   const int cpr = static_cast<int>(x.size(1) * x.element_size() / 16);
-  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3(128), dim3(256), 0, stream,
+  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3(128), dim3(256), 0,
+                     at::hip::getCurrentHIPStream(),
                      reinterpret_cast<uint4*>(x.data_ptr()),
                      cu_seqlens.data_ptr<int>(),
                      static_cast<int>(cu_seqlens.size(0)) - 1, x.size(0),
                      cpr);
-}
-
-static void check_varlen_args(const torch::Tensor& qkv,
-                              const torch::Tensor& cu_seqlens,
-                              int64_t max_seqlen, int64_t num_heads,
-                              const char* who) {
-  TORCH_CHECK(qkv.dim() == 2 && qkv.is_contiguous(), who,
-              ": qkv must be a contiguous [T_pad, 3H] matrix");
-  TORCH_CHECK(qkv.size(1) == 3 * num_heads * 64, who,
-              ": head_dim must be 64");
-  TORCH_CHECK(cu_seqlens.dim() == 1 && cu_seqlens.size(0) >= 1 &&
-                  cu_seqlens.scalar_type() == torch::kInt32 &&
-                  cu_seqlens.is_contiguous() &&
-                  cu_seqlens.device() == qkv.device(),
-              who, ": cu_seqlens must be a contiguous int32 [B+1] tensor "
-                   "on qkv's device");
-  TORCH_CHECK(max_seqlen >= 1, who, ": max_seqlen must be positive");
-  TORCH_CHECK((cu_seqlens.size(0) - 1) * num_heads <= 65535, who,
-              ": B * num_heads exceeds the grid's y limit");
-}
-
-template <typename T>
-static std::vector<torch::Tensor> attention_varlen_fwd_t(
-    torch::Tensor qkv, torch::Tensor cu_seqlens, int64_t max_seqlen,
-    int64_t num_heads, double p, int64_t seed, int64_t offset) {
-  const int64_t T_pad = qkv.size(0);
-  const int B = static_cast<int>(cu_seqlens.size(0)) - 1;
-  const int S = static_cast<int>(max_seqlen);
-  const int NH = static_cast<int>(num_heads);
-  const int H = NH * 64;
-  auto out = torch::empty({T_pad, H}, qkv.options());
-  auto lse = torch::empty({static_cast<int64_t>(B) * NH, S},
-                          qkv.options().dtype(torch::kFloat32));
-  const bool train_drop = p > 0.0;
-  const int Sw = (S + 31) / 32;
-  auto dmask = train_drop
-                   ? torch::empty({static_cast<int64_t>(B) * NH, S, Sw},
-                                  qkv.options().dtype(torch::kInt32))
-                   : torch::empty({0}, qkv.options().dtype(torch::kInt32));
-  auto stream = at::hip::getCurrentHIPStream();
-  if (T_pad > 0) zero_tail_rows(out, cu_seqlens, stream);
-  if (B == 0) return {out, lse, dmask};
-  const float scale = 1.0f / sqrtf(64.f);
-  dim3 grid((S + 127) / 128, B * NH), block(256);
-  const size_t lds = (64 * kStride + 64 * kTrStride) * sizeof(T) +
-                     4 * 64 * sizeof(float) + 128 * 2 * sizeof(uint32_t);
-  if (train_drop) {
-    const auto [thresh, p_q] = quantize_drop_p(p);
-    const int64_t words = static_cast<int64_t>(B) * NH * S * Sw;
-    hipLaunchKernelGGL(dropout_mask_kernel,
-                       dim3((words + 255) / 256), dim3(256), 0, stream,
-                       reinterpret_cast<uint32_t*>(dmask.data_ptr<int>()),
-                       words, thresh, static_cast<uint64_t>(seed),
-                       static_cast<uint64_t>(offset));
-    hipLaunchKernelGGL((attn_fwd_kernel<T, true, true>), grid, block, lds,
-                       stream, reinterpret_cast<const T*>(qkv.data_ptr()),
-                       cu_seqlens.data_ptr<int>(),
-                       reinterpret_cast<T*>(out.data_ptr()),
-                       lse.data_ptr<float>(),
-                       reinterpret_cast<const uint32_t*>(
-                           dmask.data_ptr<int>()),
-                       B, S, NH, p_q, scale,
-                       static_cast<uint64_t>(seed),
-                       static_cast<uint64_t>(offset));
-  } else {
-    hipLaunchKernelGGL((attn_fwd_kernel<T, false, true>), grid, block, lds,
-                       stream, reinterpret_cast<const T*>(qkv.data_ptr()),
-                       cu_seqlens.data_ptr<int>(),
-                       reinterpret_cast<T*>(out.data_ptr()),
-                       lse.data_ptr<float>(), nullptr, B, S, NH,
-                       static_cast<float>(p), scale,
-                       static_cast<uint64_t>(seed),
-                       static_cast<uint64_t>(offset));
-  }
-  return {out, lse, dmask};
 }
 
 // qkv [T_pad,3H] bf16 or fp16, cu_seqlens [B+1] int32 ->
@@ -1256,124 +1208,42 @@ static std::vector<torch::Tensor> attention_varlen_fwd_t(
 std::vector<torch::Tensor> attention_varlen_fwd(
     torch::Tensor qkv, torch::Tensor cu_seqlens, int64_t max_seqlen,
     int64_t num_heads, double p, int64_t seed, int64_t offset) {
-  const auto dt = qkv.scalar_type();
-  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
-              "attn_varlen_fwd: qkv must be bf16 or fp16, got ", dt);
   check_varlen_args(qkv, cu_seqlens, max_seqlen, num_heads,
                     "attn_varlen_fwd");
-  if (dt == torch::kHalf)
-    return attention_varlen_fwd_t<_Float16>(qkv, cu_seqlens, max_seqlen,
-                                            num_heads, p, seed, offset);
-  return attention_varlen_fwd_t<__bf16>(qkv, cu_seqlens, max_seqlen,
-                                        num_heads, p, seed, offset);
-}
-
-template <typename T>
-static torch::Tensor attention_varlen_bwd_t(
-    torch::Tensor dout, torch::Tensor qkv, torch::Tensor cu_seqlens,
-    int64_t max_seqlen, torch::Tensor out, torch::Tensor lse,
-    torch::Tensor dmask, int64_t num_heads, double p, int64_t seed,
-    int64_t offset) {
   const int B = static_cast<int>(cu_seqlens.size(0)) - 1;
   const int S = static_cast<int>(max_seqlen);
   const int NH = static_cast<int>(num_heads);
-  auto dqkv = torch::empty_like(qkv);
-  auto stream = at::hip::getCurrentHIPStream();
-  if (qkv.size(0) > 0) zero_tail_rows(dqkv, cu_seqlens, stream);
-  if (B == 0) return dqkv;
-  auto fopts = qkv.options().dtype(torch::kFloat32);
-  const int64_t rows = static_cast<int64_t>(B) * NH * S;
-  auto delta = torch::empty({rows}, fopts);
-
-  const int64_t delta_waves = (rows + 7) / 8;  // 8 rows per wave
-  hipLaunchKernelGGL(attn_delta_varlen_kernel<T>,
-                     dim3((delta_waves + 3) / 4), dim3(256), 0, stream,
-                     reinterpret_cast<const T*>(dout.data_ptr()),
-                     reinterpret_cast<const T*>(out.data_ptr()),
-                     delta.data_ptr<float>(), cu_seqlens.data_ptr<int>(),
-                     B, S, NH);
-
-  dim3 grid((S + 127) / 128, B * NH), block(256);
-  const size_t lds = (4 * 64 * kStride + 2 * 64 * kTrStride) *
-                         sizeof(T) +
-                     2 * 64 * sizeof(float) + 64 * 4 * sizeof(uint32_t);
-  const size_t lds_dq = (64 * kStride + 64 * kTrStride) * sizeof(T) +
-                        128 * 2 * sizeof(uint32_t);
-  HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&attn_bwd_kernel<T, true, true>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  HIP_CHECK(hipFuncSetAttribute(
-      reinterpret_cast<const void*>(&attn_bwd_kernel<T, false, true>),
-      hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-  const float scale = 1.0f / sqrtf(64.f);
-  const bool train_drop = p > 0.0;
-  const float p_q = quantize_drop_p(p).second;
-  const uint32_t* mask_ptr =
-      train_drop ? reinterpret_cast<const uint32_t*>(dmask.data_ptr<int>())
-                 : nullptr;
-  auto args = [&](auto kernel, size_t lds_bytes) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream,
-                       reinterpret_cast<const T*>(dout.data_ptr()),
-                       reinterpret_cast<const T*>(qkv.data_ptr()),
-                       cu_seqlens.data_ptr<int>(), lse.data_ptr<float>(),
-                       delta.data_ptr<float>(), mask_ptr,
-                       reinterpret_cast<T*>(dqkv.data_ptr()), B, S, NH,
-                       p_q, scale,
-                       static_cast<uint64_t>(seed),
-                       static_cast<uint64_t>(offset));
-  };
-  if (train_drop) {
-    args(attn_bwd_kernel<T, true, true>, lds);
-    args(attn_dq_kernel<T, true, true>, lds_dq);
-  } else {
-    args(attn_bwd_kernel<T, false, true>, lds);
-    args(attn_dq_kernel<T, false, true>, lds_dq);
-  }
-  return dqkv;
+  auto out = torch::empty({qkv.size(0), NH * 64}, qkv.options());
+  zero_tail_rows(out, cu_seqlens);
+  return dispatch_elem(qkv, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return attn_launch_fwd<T, true>({cu_seqlens.data_ptr<int>(), B, S, NH},
+                                    qkv, out, p, seed, offset);
+  });
 }
 
-// Packed backward -> dqkv [T_pad,3H]. All operands are checked for
-// dtype, shape and contiguity before any launch.
+// Packed backward -> dqkv [T_pad,3H]; checked like attention_bwd.
 torch::Tensor attention_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
                                    torch::Tensor cu_seqlens,
                                    int64_t max_seqlen, torch::Tensor out,
                                    torch::Tensor lse, torch::Tensor dmask,
                                    int64_t num_heads, double p,
                                    int64_t seed, int64_t offset) {
-  const auto dt = qkv.scalar_type();
-  TORCH_CHECK(dt == torch::kBFloat16 || dt == torch::kHalf,
-              "attn_varlen_bwd: qkv must be bf16 or fp16, got ", dt);
   check_varlen_args(qkv, cu_seqlens, max_seqlen, num_heads,
                     "attn_varlen_bwd");
-  TORCH_CHECK(dout.scalar_type() == dt,
-              "attn_varlen_bwd: dout dtype ", dout.scalar_type(),
-              " does not match qkv dtype ", dt);
-  TORCH_CHECK(out.scalar_type() == dt, "attn_varlen_bwd: out dtype ",
-              out.scalar_type(), " does not match qkv dtype ", dt);
-  const int64_t T_pad = qkv.size(0), H = qkv.size(1) / 3;
-  const int64_t bnh = (cu_seqlens.size(0) - 1) * num_heads;
-  TORCH_CHECK(dout.dim() == 2 && dout.size(0) == T_pad &&
-                  dout.size(1) == H && out.sizes() == dout.sizes(),
-              "attn_varlen_bwd: dout and out must be [T_pad, H]");
-  TORCH_CHECK(out.is_contiguous(), "attn_varlen_bwd: out not contiguous");
-  TORCH_CHECK(lse.scalar_type() == torch::kFloat32 && lse.is_contiguous() &&
-                  lse.numel() == bnh * max_seqlen,
-              "attn_varlen_bwd: lse must be fp32 [B*NH, max_seqlen]");
-  if (p > 0.0)
-    TORCH_CHECK(dmask.scalar_type() == torch::kInt32 &&
-                    dmask.is_contiguous() &&
-                    dmask.numel() ==
-                        bnh * max_seqlen * ((max_seqlen + 31) / 32),
-                "attn_varlen_bwd: keep-mask does not match "
-                "[B*NH, max_seqlen, ceil(max_seqlen/32)]");
-  auto dout_c = dout.contiguous();
-  if (dt == torch::kHalf)
-    return attention_varlen_bwd_t<_Float16>(dout_c, qkv, cu_seqlens,
-                                            max_seqlen, out, lse, dmask,
-                                            num_heads, p, seed, offset);
-  return attention_varlen_bwd_t<__bf16>(dout_c, qkv, cu_seqlens, max_seqlen,
-                                        out, lse, dmask, num_heads, p, seed,
-                                        offset);
+  const int B = static_cast<int>(cu_seqlens.size(0)) - 1;
+  const int S = static_cast<int>(max_seqlen);
+  const int NH = static_cast<int>(num_heads);
+  check_bwd_operands("attn_varlen_bwd", dout, qkv, out, lse, dmask,
+                     static_cast<int64_t>(B) * NH, S, p);
+  auto dqkv = torch::empty_like(qkv);
+  zero_tail_rows(dqkv, cu_seqlens);
+  dispatch_elem(qkv, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    attn_launch_bwd<T, true>({cu_seqlens.data_ptr<int>(), B, S, NH}, dout,
+                             qkv, out, lse, dmask, dqkv, p);
+  });
+  return dqkv;
 }
 
 }  // namespace bpa

@@ -16,8 +16,9 @@
 // row-major in LDS (padded stride 144 elems = 72 dwords: the
 // transpose-read's {72r*... = 8r + 2c} bank pattern covers every even
 // bank exactly once - conflict-free) and their k-strided MFMA
-// fragments produced by ds_read_b64_tr_b16 (same frag_tr recipe as
-// csrc/ops/attention.hip; semantics probe-verified by tr16_probe).
+// fragments produced by ds_read_b64_tr_b16 (frag_tr, csrc/mfma_frag.h,
+// shared with csrc/ops/attention.hip; semantics probe-verified by
+// tr16_probe, csrc/ops/mfma_probe.hip).
 // Staging is split issue-early/write-late (T14): the next k-step's
 // global loads issue before this step's 32 MFMAs per wave, so HBM
 // latency hides under the matrix work; double-buffered LDS, one
@@ -33,7 +34,7 @@
 
 #include "../common.h"
 #include "../ops.h"
-#include "../mfma_types.h"
+#include "../mfma_frag.h"
 
 namespace bpa {
 
@@ -43,26 +44,6 @@ constexpr int kBM = 128;   // C tile rows (M)
 constexpr int kBN = 128;   // C tile cols (N)
 constexpr int kBK = 32;    // K step (32-deep: 36.8 KB LDS -> 4 blocks/CU)
 constexpr int kStride = 144;  // LDS row stride (elems), tr-conflict-free
-
-// Transposed fragment from a natural [kBK][cols] row-major LDS image at
-// row stride STRIDE: element e = img[rb + g*4 + (e&3) + 16*(e>>2)][cb+li].
-// T is the 16-bit element type (__bf16 or _Float16, csrc/mfma_types.h).
-template <int STRIDE, typename T>
-__device__ __forceinline__ typename Mfma16<T>::frag frag_tr(const T* img,
-                                                            int rb, int cb) {
-  using Tr = Mfma16<T>;
-  const int lane = threadIdx.x & 63;
-  const int g = (lane >> 4) & 3, t = lane & 15;
-  const T* p0 =
-      img + (rb + g * 4 + (t >> 2)) * STRIDE + cb + (t & 3) * 4;
-  union {
-    typename Tr::frag v;
-    typename Tr::tr4 h[2];
-  } r;
-  r.h[0] = Tr::tr_read(p0);
-  r.h[1] = Tr::tr_read(p0 + 16 * STRIDE);
-  return r.v;
-}
 
 }  // namespace wg
 
@@ -152,10 +133,10 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(
       F8 af[4], bfr[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        af[t] = wg::frag_tr<wg::kStride>(dyt, kd * 32, wi * 64 + t * 16);
+        af[t] = frag_tr<wg::kStride>(dyt, kd * 32, wi * 64 + t * 16);
 #pragma unroll
       for (int t = 0; t < 4; ++t)
-        bfr[t] = wg::frag_tr<wg::kStride>(xt, kd * 32, wj * 64 + t * 16);
+        bfr[t] = frag_tr<wg::kStride>(xt, kd * 32, wj * 64 + t * 16);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ti = 0; ti < 4; ++ti)
@@ -178,111 +159,6 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int mi = m0 + wi * 64 + ti * 16 + g * 4 + r;
-        const int nj = n0 + wj * 64 + tj * 16 + li;
-        out[static_cast<int64_t>(mi) * N + nj] = acc[ti][tj][r];
-      }
-    }
-  }
-}
-
-// 256x256-tile variant: 512 threads = 8 waves as 2(M)x4(N), each wave
-// a 128x64 C tile (acc[8][4] f32x4 = 128 AGPRs). Halves the operand
-// re-read amplification of the 128^2 tile (per-tile strips are shared
-// by half as many blocks), trading occupancy (2 waves/SIMD, 1 block/CU)
-// for traffic. Selected by the host wrapper when M and N tile by 256.
-namespace wg {
-constexpr int kStride256 = 272;  // 136 dw: 8r+2c covers even banks once
-}
-
-template <typename T>
-__global__ __launch_bounds__(512) void wgrad_tn256_kernel(
-    const T* __restrict__ dy,  // [K, M]
-    const T* __restrict__ x,   // [K, N]
-    float* __restrict__ part,       // [splitk, M, N]
-    int K, int M, int N, int k_slice) {
-  using Tr = Mfma16<T>;
-  using F8 = typename Tr::frag;
-  const int m0 = blockIdx.x * 256;
-  const int n0 = blockIdx.y * 256;
-  const int kz0 = blockIdx.z * k_slice;
-  const int kz1 = min(K, kz0 + k_slice);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 2, wj = wave & 3;  // 2x4 wave grid: 128x64 each
-  const int g = (lane >> 4), li = lane & 15;
-
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  T* lds = reinterpret_cast<T*>(smem);
-  constexpr int kTile = wg::kBK * wg::kStride256;
-
-  // staging: 32 rows x 256 cols = 16 bf16 per thread per matrix
-  const int st_r = tid >> 4;
-  const int st_c = (tid & 15) * 16;
-
-  uint4 pf_dy[2], pf_x[2];
-  auto issue_loads = [&](int k0) {
-    const int krow = min(k0 + st_r, K - 1);
-    const uint4* ds = reinterpret_cast<const uint4*>(
-        dy + static_cast<int64_t>(krow) * M + m0 + st_c);
-    const uint4* xs = reinterpret_cast<const uint4*>(
-        x + static_cast<int64_t>(krow) * N + n0 + st_c);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      pf_dy[q] = ds[q];
-      pf_x[q] = xs[q];
-    }
-  };
-
-  f32x4 acc[8][4] = {};
-  issue_loads(kz0);
-
-  int buf = 0;
-  for (int k0 = kz0; k0 < kz1; k0 += wg::kBK) {
-    if (k0 + st_r >= kz1) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) pf_dy[q] = pf_x[q] = uint4{0, 0, 0, 0};
-    }
-    const int boff = buf * 2 * kTile;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      *reinterpret_cast<uint4*>(
-          &lds[boff + st_r * wg::kStride256 + st_c + 8 * q]) = pf_dy[q];
-      *reinterpret_cast<uint4*>(
-          &lds[boff + kTile + st_r * wg::kStride256 + st_c + 8 * q]) =
-          pf_x[q];
-    }
-    __syncthreads();
-    issue_loads(k0 + wg::kBK < kz1 ? k0 + wg::kBK : k0);
-
-    const T* dyt = lds + boff;
-    const T* xt = lds + boff + kTile;
-    {
-      F8 bfr[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        bfr[t] = wg::frag_tr<wg::kStride256>(xt, 0, wj * 64 + t * 16);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ti = 0; ti < 8; ++ti) {
-        const F8 af =
-            wg::frag_tr<wg::kStride256>(dyt, 0, wi * 128 + ti * 16);
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj)
-          acc[ti][tj] = Tr::mfma(af, bfr[tj], acc[ti][tj]);
-      }
-      __builtin_amdgcn_s_setprio(0);
-    }
-    buf ^= 1;
-  }
-
-  float* out = part + static_cast<int64_t>(blockIdx.z) * M * N;
-#pragma unroll
-  for (int ti = 0; ti < 8; ++ti) {
-#pragma unroll
-    for (int tj = 0; tj < 4; ++tj) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int mi = m0 + wi * 128 + ti * 16 + g * 4 + r;
         const int nj = n0 + wj * 64 + tj * 16 + li;
         out[static_cast<int64_t>(mi) * N + nj] = acc[ti][tj][r];
       }
@@ -335,9 +211,7 @@ static torch::Tensor wgrad_tn_t(torch::Tensor dy, torch::Tensor x,
   const int K = dy.size(0), M = dy.size(1), N = x.size(1);
   TORCH_CHECK(x.size(0) == K, "wgrad_tn: K mismatch");
   TORCH_CHECK(wgrad_tn_supported(K, M, N), "wgrad_tn: unsupported shape");
-  const bool big = false;  // 256-tile variant measured SLOWER (1 block/CU cannot hide latency); kept for reference
-  const int bm = big ? 256 : wg::kBM, bn = big ? 256 : wg::kBN;
-  const int tiles = (M / bm) * (N / bn);
+  const int tiles = (M / wg::kBM) * (N / wg::kBN);
   // k-step depth: 64 halves barriers / doubles the MFMA run per tile
   // at 2 blocks/CU; override with BPA_WGRAD_BK for sweeps
   const char* env_bk = getenv("BPA_WGRAD_BK");  // per-call: sweepable
@@ -359,34 +233,22 @@ static torch::Tensor wgrad_tn_t(torch::Tensor dy, torch::Tensor x,
                            dy.options().dtype(torch::kFloat32));
   auto out = torch::empty({static_cast<int64_t>(M), N}, dy.options());
   auto stream = at::hip::getCurrentHIPStream();
-  dim3 grid(M / bm, N / bn, splitk), block(big ? 512 : 256);
-  const size_t lds =
-      4 * bk * (big ? wg::kStride256 : wg::kStride) * sizeof(T);
-  if (big) {
+  dim3 grid(M / wg::kBM, N / wg::kBN, splitk), block(256);
+  // two double-buffered [bk][kStride] images (dy, x)
+  const size_t lds = 4 * bk * wg::kStride * sizeof(T);
+  auto launch = [&](auto kernel) {
     HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_tn256_kernel<T>),
+        reinterpret_cast<const void*>(kernel),
         hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL(wgrad_tn256_kernel<T>, grid, block, lds, stream,
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream,
                        reinterpret_cast<const T*>(dy.data_ptr()),
                        reinterpret_cast<const T*>(x.data_ptr()),
                        part.data_ptr<float>(), K, M, N, k_slice);
-  } else if (bk == 64) {
-    HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_tn_kernel<T, 64>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((wgrad_tn_kernel<T, 64>), grid, block, lds, stream,
-                       reinterpret_cast<const T*>(dy.data_ptr()),
-                       reinterpret_cast<const T*>(x.data_ptr()),
-                       part.data_ptr<float>(), K, M, N, k_slice);
-  } else {
-    HIP_CHECK(hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&wgrad_tn_kernel<T, 32>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((wgrad_tn_kernel<T, 32>), grid, block, lds, stream,
-                       reinterpret_cast<const T*>(dy.data_ptr()),
-                       reinterpret_cast<const T*>(x.data_ptr()),
-                       part.data_ptr<float>(), K, M, N, k_slice);
-  }
+  };
+  if (bk == 64)
+    launch(&wgrad_tn_kernel<T, 64>);
+  else
+    launch(&wgrad_tn_kernel<T, 32>);
   const int64_t mn = static_cast<int64_t>(M) * N;
   hipLaunchKernelGGL(wgrad_combine_kernel<T>, dim3((mn / 4 + 255) / 256),
                      dim3(256), 0, stream, part.data_ptr<float>(),

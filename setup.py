@@ -25,6 +25,7 @@ sources = [
     "csrc/ops/varlen.hip",
     "csrc/ops/wgrad.hip",
     "csrc/ops/mlm_head.hip",
+    "csrc/ops/mfma_probe.hip",
     "csrc/ops/gemm_epilogue.cpp",
     "csrc/optim/multi_tensor.hip",
     "csrc/tok/tokenizer.cpp",

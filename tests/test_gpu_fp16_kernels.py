@@ -188,6 +188,50 @@ def test_mixed_dtype_operands_raise():
         ext().wgrad_tn(dy, x)
 
 
+def test_attention_bwd_operand_checks_raise():
+    """Malformed operands of the padded backward are rejected on the host,
+    naming the operand; nothing is launched (dqkv is never allocated)."""
+    torch.manual_seed(23)
+    B, S, NH = 1, 16, 2
+    H = NH * 64
+    p = 0.1
+    qkv = (torch.randn(B, S, 3 * H, device=DEV) * 0.5).half()
+    seqlens = torch.full((B,), S, device=DEV, dtype=torch.int32)
+    out, lse, m = ext().attention_fwd(qkv, seqlens, NH, 0.0, 0, 0)
+    _o, _l, dmask = ext().attention_fwd(qkv, seqlens, NH, p, 77, 5)
+    dout = torch.randn(B, S, H, device=DEV).half()
+
+    def bwd(out=out, lse=lse, mask=m, seqlens=seqlens, p=0.0):
+        return ext().attention_bwd(
+            dout, qkv, seqlens, out, lse, mask, NH, p, 77, 5
+        )
+
+    bwd()  # the well-formed call goes through
+    bwd(mask=dmask, p=p)
+    with pytest.raises(RuntimeError, match="attn_bwd: lse dtype BFloat16"):
+        bwd(lse=lse.bfloat16())
+    with pytest.raises(RuntimeError, match="attn_bwd: lse must be"):
+        bwd(lse=lse[:, :-1])
+    with pytest.raises(RuntimeError, match="attn_bwd: keep-mask must be"):
+        bwd(mask=dmask.flatten()[:-1], p=p)
+    wide = torch.zeros(B, S, 2 * H, device=DEV, dtype=F16)
+    out_view = wide[:, :, :H]
+    assert out_view.shape == out.shape and not out_view.is_contiguous()
+    with pytest.raises(RuntimeError, match="attn_bwd: out must be contig"):
+        bwd(out=out_view)
+    longer = torch.full((B + 1,), S, device=DEV, dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="attn_bwd: seqlens must have"):
+        bwd(seqlens=longer)
+
+
+def test_attention_fwd_seqlens_length_raises():
+    B, S, NH = 1, 16, 2
+    qkv = torch.zeros(B, S, 3 * NH * 64, device=DEV, dtype=F16)
+    longer = torch.full((B + 1,), S, device=DEV, dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="attn_fwd: seqlens must have"):
+        ext().attention_fwd(qkv, longer, NH, 0.0, 0, 0)
+
+
 # ---------------------------------------------------------------------------
 # split-K MFMA wgrad GEMM
 # ---------------------------------------------------------------------------
