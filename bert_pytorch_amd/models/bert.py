@@ -159,20 +159,31 @@ class _PackedQKV(nn.Module):
                 self.qkv_bias.copy_(torch.cat([p.reshape(h) for p in parts_b], 0))
 
 
+class _LinearNoBias(nn.Linear):
+    """``nn.Linear`` whose forward is the bias-free GEMM: the bias is
+    applied by the fused bias+dropout+residual+LN kernel of the owning
+    block. Being a module that is really called, it is visible to module
+    hooks (optim/kfac.py collects its factors there); parameters,
+    initialisation and state-dict keys are ``nn.Linear``'s."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return ops.linear_nobias(x, self.weight)
+
+
 class BertSelfOutput(nn.Module):
     """Attention out-projection + fused bias/dropout/residual/LN
     (reference: src/modeling.py:432-443)."""
 
     def __init__(self, config: BertConfig):
         super().__init__()
-        self.dense = nn.Linear(config.hidden_size, config.hidden_size)
+        self.dense = _LinearNoBias(config.hidden_size, config.hidden_size)
         self.LayerNorm = ops.FusedLayerNorm(config.hidden_size, eps=1e-12)
         self.dropout_prob = config.hidden_dropout_prob
 
     def forward(self, hidden: torch.Tensor, residual: torch.Tensor, fork: bool = False):
         """``fork``: return the output as a pair of handles, one per
         consumer (ops/fused_residual.py)."""
-        y = ops.linear_nobias(hidden, self.dense.weight)  # bias in fusion
+        y = self.dense(hidden)  # bias in fusion
         return ops.fused_bias_dropout_residual_ln(
             y, self.dense.bias, residual,
             self.LayerNorm.weight, self.LayerNorm.bias,
@@ -231,12 +242,12 @@ class BertIntermediate(nn.Module):
 class BertOutput(nn.Module):
     def __init__(self, config: BertConfig):
         super().__init__()
-        self.dense = nn.Linear(config.intermediate_size, config.hidden_size)
+        self.dense = _LinearNoBias(config.intermediate_size, config.hidden_size)
         self.LayerNorm = ops.FusedLayerNorm(config.hidden_size, eps=1e-12)
         self.dropout_prob = config.hidden_dropout_prob
 
     def forward(self, hidden: torch.Tensor, residual: torch.Tensor, fork: bool = False):
-        y = ops.linear_nobias(hidden, self.dense.weight)
+        y = self.dense(hidden)
         return ops.fused_bias_dropout_residual_ln(
             y, self.dense.bias, residual,
             self.LayerNorm.weight, self.LayerNorm.bias,
@@ -260,7 +271,13 @@ class BertLayer(nn.Module):
         the layer the attention junction's output is always forked
         between FFN1 and the FFN residual."""
         attn, attn_res = self.attention(x, seqlens, max_seqlen, fork=True)
-        if self._ffn_gelu and ops.ffn_supported(attn):
+        # forward hooks on output.dense (K-FAC factor collection) only
+        # fire on the module route, so they switch the fused route off
+        if (
+            self._ffn_gelu
+            and not self.output.dense._forward_hooks
+            and ops.ffn_supported(attn)
+        ):
             # GELU folded into the FFN GEMM epilogues (ops/ffn.py);
             # FFN2's bias stays fused in the bdrl kernel below
             y = ops.fused_ffn(

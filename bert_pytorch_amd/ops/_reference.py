@@ -152,6 +152,31 @@ def unpack_rows(y: torch.Tensor, dest: torch.Tensor, rows: int) -> torch.Tensor:
     return torch.where(keep.unsqueeze(-1), gathered, torch.zeros_like(gathered))
 
 
+def kfac_factor_update(
+    x2d: torch.Tensor,
+    factor: torch.Tensor,
+    beta: Optional[float],
+    alpha: Optional[float],
+    has_bias: bool,
+    coef: Optional[torch.Tensor] = None,
+) -> None:
+    """factor <- beta*factor + alpha*[x,1]^T[x,1], in place, in fp32.
+
+    ``coef`` ({beta, alpha} as a tensor) replaces the two floats; a zero
+    ``coef[1]`` leaves ``factor`` untouched whatever ``x2d`` holds.
+    """
+    a = x2d.float()
+    if has_bias:
+        ones = torch.ones(a.shape[0], 1, dtype=a.dtype, device=a.device)
+        a = torch.cat([a, ones], dim=1)
+    cov = a.t() @ a
+    if coef is None:
+        factor.mul_(beta).add_(cov, alpha=alpha)
+        return
+    new = factor * coef[0] + cov * coef[1]
+    factor.copy_(torch.where(coef[1] != 0, new, factor))
+
+
 def cross_entropy(
     logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -1
 ) -> torch.Tensor:

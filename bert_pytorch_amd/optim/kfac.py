@@ -9,11 +9,36 @@ Per eligible linear layer l with input activations a [N, in] and
 pre-activation output gradients g [N, out], maintains running Kronecker
 factors
 
-    A_l = E[a aT]   (bias handled by appending a ones column)
+    A_l = E[a aT]   (bias handled as a ones column, never materialised
+                     on the native path)
     G_l = E[g gT]   (per-sample scale: g is multiplied by N because the
                      loss is batch-mean reduced)
 
-accumulated in forward/backward hooks each training micro-batch, and
+Eligible layers are every ``nn.Linear`` and the packed QKV projection
+outside ``skip_layers``: in the encoder that is QKV, the attention
+output projection and the FFN output projection of every layer (the
+last two are ``nn.Linear`` subclasses whose forward is the bias-free
+GEMM, so module hooks see them; while they carry forward hooks the
+layer does not take the fused-FFN route). ``LinearActivation`` (FFN1,
+pooler), embeddings and the LM head stay first-order, as in the
+reference.
+
+Each update is ``factor <- beta*factor + alpha*[a,1]T[a,1]`` through
+``ops.factor_update``: on 16-bit GPU activations with in % 128 == 0 and
+N >= 256 the symmetric split-K MFMA kernel (csrc/ops/kfac_factor.hip),
+otherwise the eager composite (NSP head, pooled inputs, fp32, CPU).
+``native_factors=False`` forces the composite; ``native_updates`` counts
+the updates that ran the kernel. An fp32 activation that reaches a hook
+under autocast is cast to the autocast dtype, which is what the layer's
+GEMM consumes.
+
+With ``grad_scaler`` (the training loop's GradScaler) G is accumulated
+from unscaled gradients: alpha is divided by scale^2 on the device. A G
+update whose g holds Inf/NaN (an overflowing fp16 micro-batch, which the
+scaler will skip) is dropped: {beta, alpha} become {1, 0} on the device,
+without a host sync, and G stays bit-identical. A updates are not gated.
+
+Factors are accumulated in forward/backward hooks each training micro-batch, and
 every ``inv_update_interval`` optimizer steps recomputes damped inverses
 
     A_l^-1 = (A_l + sqrt(damping) I)^-1,  G_l^-1 = (G_l + sqrt(damping) I)^-1
@@ -40,6 +65,9 @@ import torch
 import torch.distributed as dist
 from torch import nn
 
+from .. import ops
+from ..ops.kfac_factor import device_coef
+
 __all__ = ["KFAC"]
 
 _DEFAULT_SKIP = ("BertLMPredictionHead", "embedding")
@@ -50,7 +78,8 @@ def _is_dist() -> bool:
 
 
 class _LayerState:
-    __slots__ = ("module", "name", "has_bias", "A", "G", "A_inv", "G_inv")
+    __slots__ = ("module", "name", "has_bias", "A", "G", "A_inv", "G_inv",
+                 "G_started")
 
     def __init__(self, module: nn.Module, name: str, has_bias: bool):
         self.module = module
@@ -60,6 +89,9 @@ class _LayerState:
         self.G: Optional[torch.Tensor] = None
         self.A_inv: Optional[torch.Tensor] = None
         self.G_inv: Optional[torch.Tensor] = None
+        # device flag (0/1), only kept under a GradScaler: G has had its
+        # first update that was not dropped for a non-finite gradient
+        self.G_started: Optional[torch.Tensor] = None
 
     def weight(self) -> nn.Parameter:
         mod = self.module
@@ -75,9 +107,10 @@ class _LayerState:
 class KFAC:
     """Hook-based distributed K-FAC gradient preconditioner.
 
-    Eligible layers: plain ``nn.Linear`` and the packed QKV projection
-    (the reference's kfac likewise only matched ``linear`` modules, so
-    fused LinearActivation/embeddings/LM head stay first-order).
+    Eligible layers: ``nn.Linear`` (subclasses included) and the packed
+    QKV projection (the reference's kfac likewise only matched ``linear``
+    modules, so fused LinearActivation/embeddings/LM head stay
+    first-order).
     """
 
     def __init__(
@@ -92,6 +125,8 @@ class KFAC:
         lr: float = 1.0,
         skip_layers: Sequence[str] = _DEFAULT_SKIP,
         inv_dtype: torch.dtype = torch.float32,
+        grad_scaler=None,
+        native_factors: Optional[bool] = None,
     ):
         if hasattr(model, "module"):  # unwrap DDP
             model = model.module
@@ -103,6 +138,12 @@ class KFAC:
         self.kl_clip = float(kl_clip)
         self.lr = float(lr)
         self.inv_dtype = inv_dtype
+        # torch.amp.GradScaler of the training loop (or None): G factors
+        # are accumulated from unscaled gradients
+        self.grad_scaler = grad_scaler
+        # None: HIP factor kernel where it applies; False: eager composite
+        self.native_factors = native_factors
+        self.native_updates = 0  # factor updates that ran the HIP kernel
         self._steps = 0
         self._hooks: List[torch.utils.hooks.RemovableHandle] = []
         self.layers: List[_LayerState] = []
@@ -143,28 +184,62 @@ class KFAC:
 
         return hook
 
+    def _factor_update(self, x2d, factor, beta, alpha, has_bias, coef=None):
+        native = ops.factor_update(
+            x2d, factor, beta, alpha, has_bias, coef=coef,
+            native=self.native_factors,
+        )
+        self.native_updates += int(native)
+
     @torch.no_grad()
     def _update_A(self, state: _LayerState, a: torch.Tensor) -> None:
-        a = a.reshape(-1, a.shape[-1]).float()
-        if state.has_bias:
-            ones = torch.ones(a.shape[0], 1, dtype=a.dtype, device=a.device)
-            a = torch.cat([a, ones], dim=1)
-        cov = a.t() @ a / a.shape[0]
+        a = a.reshape(-1, a.shape[-1])
+        if a.is_cuda and a.dtype == torch.float32 and torch.is_autocast_enabled():
+            # what the layer's GEMM consumes under autocast
+            a = a.to(torch.get_autocast_dtype("cuda"))
+        n, d = a.shape[0], a.shape[1] + int(state.has_bias)
         if state.A is None:
-            state.A = cov
+            state.A = torch.zeros(d, d, dtype=torch.float32, device=a.device)
+            beta, alpha = 0.0, 1.0 / n
         else:
-            state.A.mul_(self.factor_decay).add_(cov, alpha=1 - self.factor_decay)
+            beta, alpha = self.factor_decay, (1 - self.factor_decay) / n
+        self._factor_update(a, state.A, beta, alpha, state.has_bias)
 
     @torch.no_grad()
     def _update_G(self, state: _LayerState, g: torch.Tensor) -> None:
-        g = g.reshape(-1, g.shape[-1]).float()
-        n = g.shape[0]
+        g = g.reshape(-1, g.shape[-1])
+        n, d = g.shape
         # batch-mean loss => per-sample grads are g*n; cov = (g n)T (g n)/n
-        cov = g.t() @ g * n
-        if state.G is None:
-            state.G = cov
+        fresh = state.G is None
+        if fresh:
+            state.G = torch.zeros(d, d, dtype=torch.float32, device=g.device)
+        first = device_coef(0.0, float(n), g.device)
+        ema = device_coef(
+            self.factor_decay, (1 - self.factor_decay) * n, g.device
+        )
+        # {beta, alpha} built on the device, no host sync: the loss scale
+        # is divided out of alpha, and a non-finite g (an overflowing
+        # fp16 micro-batch) turns the update into {1, 0}, which leaves G
+        # untouched
+        ok = torch.isfinite(g).all()
+        scaler = self.grad_scaler
+        if scaler is not None and scaler.is_enabled():
+            # a scaler that starts too high drops the first micro-batches:
+            # whether G has had its first real update is device state too
+            if state.G_started is None:
+                state.G_started = torch.full(
+                    (), 0.0 if fresh else 1.0, device=g.device
+                )
+            coef = torch.where(state.G_started > 0, ema, first)
+            state.G_started = torch.maximum(state.G_started, ok.float())
+            scale = scaler.scale(
+                torch.ones((), dtype=torch.float32, device=g.device)
+            )
+            coef = coef / torch.stack([torch.ones_like(scale), scale * scale])
         else:
-            state.G.mul_(self.factor_decay).add_(cov, alpha=1 - self.factor_decay)
+            coef = first if fresh else ema
+        coef = torch.where(ok, coef, device_coef(1.0, 0.0, g.device))
+        self._factor_update(g, state.G, None, None, False, coef=coef)
 
     # -- inverses ----------------------------------------------------------
 

@@ -41,6 +41,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MFMA MLM-decoder GEMM with fused bias + CE-forward epilogue");
   m.def("mlm_head_supported", &bpa::mlm_head_supported);
   m.def("wgrad_tn_profitable", &bpa::wgrad_tn_profitable);
+  m.def("kfac_factor_update", &bpa::kfac_factor_update,
+        "in-place K-FAC factor EMA: symmetric MFMA x^T x (+ bias column)",
+        py::arg("x"), py::arg("factor"), py::arg("coef"),
+        py::arg("has_bias"), py::arg("splitk_override") = 0);
+  m.def("kfac_factor_supported", &bpa::kfac_factor_supported);
   m.def("multi_tensor_l2norm_sq", &bpa::multi_tensor_l2norm_sq);
   m.def("multi_tensor_clip_scale", &bpa::multi_tensor_clip_scale);
   m.def("fused_lamb", &bpa::fused_lamb);

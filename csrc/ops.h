@@ -84,6 +84,12 @@ std::vector<torch::Tensor> mlm_head_fwd(torch::Tensor h, torch::Tensor w,
 bool mlm_head_supported(int64_t P, int64_t V, int64_t K);
 bool wgrad_tn_supported(int64_t K, int64_t M, int64_t N);
 bool wgrad_tn_profitable(int64_t K, int64_t M, int64_t N);
+// kfac_factor.hip: factor[D,D] = coef[0]*factor + coef[1]*cov([x,1] or x),
+// D = K + has_bias; coef = {beta, alpha} fp32 on the device
+void kfac_factor_update(torch::Tensor x, torch::Tensor factor,
+                        torch::Tensor coef, bool has_bias,
+                        int64_t splitk_override);
+bool kfac_factor_supported(int64_t N, int64_t K);
 torch::Tensor attention_bwd(torch::Tensor dout, torch::Tensor qkv,
                             torch::Tensor seqlens, torch::Tensor out,
                             torch::Tensor lse, torch::Tensor dmask,

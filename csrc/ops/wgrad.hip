@@ -22,7 +22,9 @@
 // Staging is split issue-early/write-late (T14): the next k-step's
 // global loads issue before this step's 32 MFMAs per wave, so HBM
 // latency hides under the matrix work; double-buffered LDS, one
-// barrier pair per k-step.
+// barrier pair per k-step. The k-loop itself is tn_mainloop
+// (tn_mainloop.h), shared with the K-FAC factor kernel
+// (kfac_factor.hip).
 //
 // Reference op being replaced: the implicit wgrad GEMMs of
 // src/modeling.py's nn.Linear calls (SURVEY.md §2.4 "Backward of all
@@ -34,18 +36,9 @@
 
 #include "../common.h"
 #include "../ops.h"
-#include "../mfma_frag.h"
+#include "tn_mainloop.h"
 
 namespace bpa {
-
-namespace wg {
-
-constexpr int kBM = 128;   // C tile rows (M)
-constexpr int kBN = 128;   // C tile cols (N)
-constexpr int kBK = 32;    // K step (32-deep: 36.8 KB LDS -> 4 blocks/CU)
-constexpr int kStride = 144;  // LDS row stride (elems), tr-conflict-free
-
-}  // namespace wg
 
 // grid: (M/128, N/128, splitk); block 256. BK = 32 or 64: 64 halves
 // the barrier count and doubles the MFMA run per staged tile (36.8 ->
@@ -57,8 +50,6 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(
     const T* __restrict__ x,   // [K, N]
     float* __restrict__ part,       // [splitk, M, N]
     int K, int M, int N, int k_slice) {
-  using Tr = Mfma16<T>;
-  using F8 = typename Tr::frag;
   const int m0 = blockIdx.x * wg::kBM;
   const int n0 = blockIdx.y * wg::kBN;
   const int kz0 = blockIdx.z * k_slice;
@@ -74,81 +65,9 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(
   // ds_write cost plus per-store 64-bit compares)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* lds = reinterpret_cast<T*>(smem);
-  constexpr int kTile = BK * wg::kStride;
-  constexpr int kTPR = 256 / BK;      // staging threads per k-row
-  constexpr int kSlots = BK / 16;     // uint4 slots per thread per matrix
-
-  // staging map: thread -> (row r, kSlots 8-elem slots 8*kTPR apart);
-  // at BK=32 each ds_write_b128's 8-lane group covers one 128-B row
-  // (conflict-free); at BK=64 it covers two half-rows (2-way on half
-  // the banks - measured cheaper than the extra barriers it replaces)
-  const int st_r = tid / kTPR;
-  const int st_c = (tid % kTPR) * 8;
-
-  // Prefetch loads are UNCONDITIONAL with the row clamped to the last
-  // valid one (a conditional load/zero branch inside the loop-carried
-  // lambda segfaults hipcc/ROCm 7.2's gfx950 optimizer at -O2/-O3);
-  // rows past the slice end are zeroed at LDS-write time instead.
-  uint4 pf_dy[kSlots], pf_x[kSlots];
-  auto issue_loads = [&](int k0) {
-    const int krow = min(k0 + st_r, K - 1);  // clamp: always legal memory
-    const uint4* ds = reinterpret_cast<const uint4*>(
-        dy + static_cast<int64_t>(krow) * M + m0 + st_c);
-    const uint4* xs = reinterpret_cast<const uint4*>(
-        x + static_cast<int64_t>(krow) * N + n0 + st_c);
-#pragma unroll
-    for (int q = 0; q < kSlots; ++q) {
-      pf_dy[q] = ds[q * kTPR];
-      pf_x[q] = xs[q * kTPR];
-    }
-  };
 
   f32x4 acc[4][4] = {};
-  issue_loads(kz0);
-
-  int buf = 0;
-  for (int k0 = kz0; k0 < kz1; k0 += BK) {
-    // write the in-flight k-step into buf (T14 write-late); zero rows
-    // past the slice end so the clamped prefetch cannot contaminate
-    if (k0 + st_r >= kz1) {
-#pragma unroll
-      for (int q = 0; q < kSlots; ++q) pf_dy[q] = pf_x[q] = uint4{0, 0, 0, 0};
-    }
-    const int boff = buf * 2 * kTile;
-#pragma unroll
-    for (int q = 0; q < kSlots; ++q) {
-      *reinterpret_cast<uint4*>(
-          &lds[boff + st_r * wg::kStride + st_c + 8 * kTPR * q]) = pf_dy[q];
-      *reinterpret_cast<uint4*>(
-          &lds[boff + kTile + st_r * wg::kStride + st_c + 8 * kTPR * q]) =
-          pf_x[q];
-    }
-    __syncthreads();
-    issue_loads(k0 + BK < kz1 ? k0 + BK : k0);  // T14 issue-early
-
-    const T* dyt = lds + boff;
-    const T* xt = lds + boff + kTile;
-#pragma unroll
-    for (int kd = 0; kd < BK / 32; ++kd) {
-      F8 af[4], bfr[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        af[t] = frag_tr<wg::kStride>(dyt, kd * 32, wi * 64 + t * 16);
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        bfr[t] = frag_tr<wg::kStride>(xt, kd * 32, wj * 64 + t * 16);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int ti = 0; ti < 4; ++ti)
-#pragma unroll
-        for (int tj = 0; tj < 4; ++tj)
-          acc[ti][tj] = Tr::mfma(af[ti], bfr[tj], acc[ti][tj]);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    // no trailing barrier: the next iteration writes the OTHER buffer,
-    // whose last readers finished before this iteration's barrier
-    buf ^= 1;
-  }
+  tn_mainloop<T, BK>(dy, M, m0, x, N, n0, K, kz0, kz1, lds, acc);
 
   // epilogue: fp32 partial tile [M,N] for this k-slice
   float* out = part + static_cast<int64_t>(blockIdx.z) * M * N;

@@ -256,6 +256,7 @@ def prepare_optimizers(args, model, resume_state):
             factor_update_interval=args.kfac_factor_interval,
             inv_update_interval=args.kfac_inv_interval,
             skip_layers=args.kfac_skip_layers,
+            grad_scaler=scaler,
         )
 
     if resume_state is not None:

@@ -24,6 +24,7 @@ sources = [
     "csrc/ops/attention.hip",
     "csrc/ops/varlen.hip",
     "csrc/ops/wgrad.hip",
+    "csrc/ops/kfac_factor.hip",
     "csrc/ops/mlm_head.hip",
     "csrc/ops/mfma_probe.hip",
     "csrc/ops/gemm_epilogue.cpp",
