@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import _reference, extension, use_native
+from .grad_accum import accum_target
 
 
 class _FusedBiasGelu(torch.autograd.Function):
@@ -20,6 +21,7 @@ class _FusedBiasGelu(torch.autograd.Function):
         x2d = x.contiguous().view(-1, x.shape[-1])
         y = ext.bias_gelu_fwd(x2d, bias)
         ctx.save_for_backward(x2d, bias)
+        ctx.bias = bias  # the caller's tensor, for the gate
         ctx.shape = x.shape
         return y.view(x.shape)
 
@@ -28,7 +30,9 @@ class _FusedBiasGelu(torch.autograd.Function):
         ext = extension()
         x2d, bias = ctx.saved_tensors
         dy2d = dy.contiguous().view(-1, dy.shape[-1])
-        dx, dbias = ext.bias_gelu_bwd(dy2d, x2d, bias)
+        # added into bias.grad by the fold where the gate allows (dbias None)
+        acc = accum_target(ctx.bias, torch.float32, bias.shape)
+        dx, dbias = ext.bias_gelu_bwd(dy2d, x2d, bias, dbias_acc=acc)
         return dx.view(ctx.shape), dbias
 
 

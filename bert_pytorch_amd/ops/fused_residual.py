@@ -23,6 +23,7 @@ from typing import Optional, Tuple, Union
 import torch
 
 from . import _reference, extension, use_native
+from .grad_accum import accum_target
 from .rng import next_philox
 
 
@@ -39,6 +40,7 @@ class _FusedBiasDropoutResidualLN(torch.autograd.Function):
             x2d, bias, r2d, weight, ln_bias, p if training else 0.0, eps, seed, offset
         )
         ctx.save_for_backward(z, mask, weight, mean, rstd)
+        ctx.params = (bias, weight, ln_bias)  # the caller's tensors
         ctx.p = p if training else 0.0
         ctx.has_bias = bias is not None
         ctx.shape = x.shape
@@ -60,8 +62,13 @@ class _FusedBiasDropoutResidualLN(torch.autograd.Function):
         dy2d = dy.contiguous().view(-1, dy.shape[-1])
         if dy_fork is not None:
             dy_fork = dy_fork.contiguous().view(-1, dy.shape[-1])
+        # bias, gamma and beta gradients are added into .grad by the fold
+        # where the gate allows, and come back as None
+        gbias, gw, gb = (accum_target(p, torch.float32, weight.shape)
+                         for p in ctx.params)
         dx, dbias, dz, dw, db = ext.bias_dropout_residual_ln_bwd(
-            dy2d, z, mask, weight, mean, rstd, ctx.p, ctx.has_bias, dy_fork
+            dy2d, z, mask, weight, mean, rstd, ctx.p, ctx.has_bias, dy_fork,
+            dgamma_acc=gw, dbeta_acc=gb, dbias_acc=gbias,
         )
         return (
             dx.view(ctx.shape),

@@ -14,6 +14,7 @@ from __future__ import annotations
 import torch
 
 from . import _reference, extension, use_native
+from .grad_accum import accum_target
 
 
 class _FusedLayerNorm(torch.autograd.Function):
@@ -23,6 +24,7 @@ class _FusedLayerNorm(torch.autograd.Function):
         x2d = x.contiguous().view(-1, x.shape[-1])
         y, mean, rstd = ext.ln_fwd(x2d, weight, bias, eps)
         ctx.save_for_backward(x2d, weight, mean, rstd)
+        ctx.params = (weight, bias)  # the caller's tensors, for the gate
         ctx.shape = x.shape
         return y.view(x.shape)
 
@@ -31,7 +33,11 @@ class _FusedLayerNorm(torch.autograd.Function):
         ext = extension()
         x2d, weight, mean, rstd = ctx.saved_tensors
         dy2d = dy.contiguous().view(-1, dy.shape[-1])
-        dx, dw, db = ext.ln_bwd(dy2d, x2d, weight, mean, rstd)
+        # added into .grad by the fold where the gate allows (then None)
+        gw, gb = (accum_target(p, torch.float32, weight.shape)
+                  for p in ctx.params)
+        dx, dw, db = ext.ln_bwd(dy2d, x2d, weight, mean, rstd,
+                                dgamma_acc=gw, dbeta_acc=gb)
         return dx.view(ctx.shape), dw, db, None
 
 

@@ -21,10 +21,17 @@ import torch
 import torch.nn.functional as F
 
 from . import extension, use_native
+from .grad_accum import accum_target
 
 
-def _wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
+def _wgrad(dy2: torch.Tensor, x2: torch.Tensor, param=None):
     """dW = dy2^T @ x2 via the split-K kernel when supported.
+
+    ``param``: the weight the Function was given. Where the split-K kernel
+    runs and the gate (ops/grad_accum.py) allows it, dW is added into
+    ``param.grad`` by the combine kernel and ``None`` is returned. The
+    library product below never is: a ``beta = 1`` GEMM rounds once where
+    store-then-add rounds twice, which would change bits.
 
     bf16 or fp16, both operands alike. ``wgrad_tn_profitable``'s
     thresholds were tuned against the bf16 library GEMMs and fp16 keeps
@@ -40,7 +47,8 @@ def _wgrad(dy2: torch.Tensor, x2: torch.Tensor) -> torch.Tensor:
             dy2.shape[0], dy2.shape[1], x2.shape[1]
         )
     ):
-        return extension().wgrad_tn(dy2, x2)
+        acc = accum_target(param, dy2.dtype, (dy2.shape[1], x2.shape[1]))
+        return extension().wgrad_tn(dy2, x2, acc=acc)
     return dy2.t() @ x2
 
 
@@ -49,6 +57,7 @@ class _LinearNoBias(torch.autograd.Function):
     def forward(ctx, x, weight):
         x2 = x.reshape(-1, x.shape[-1])
         ctx.save_for_backward(x2, weight)
+        ctx.weight = weight  # the caller's tensor, for the gate
         ctx.x_shape = x.shape
         y = F.linear(x2, weight, None)
         return y.view(*x.shape[:-1], weight.shape[0])
@@ -58,7 +67,7 @@ class _LinearNoBias(torch.autograd.Function):
         x2, weight = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         dx = dy2 @ weight
-        dw = _wgrad(dy2, x2.contiguous())
+        dw = _wgrad(dy2, x2.contiguous(), ctx.weight)
         return dx.view(ctx.x_shape), dw
 
 

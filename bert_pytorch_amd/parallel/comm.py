@@ -115,6 +115,11 @@ def wrap_ddp(
     # CPU/gloo module on a GPU box must not get device_ids.
     on_cuda = any(p.is_cuda for p in model.parameters())
     device_ids = [local_rank] if on_cuda else None
+    # DDP's reducer hooks sit on the AccumulateGrad nodes, which a backward
+    # that adds into .grad itself leaves without a gradient
+    from ..ops import grad_accum  # noqa: PLC0415
+
+    grad_accum.set_enabled(False)
     ddp = torch.nn.parallel.DistributedDataParallel(
         model,
         device_ids=device_ids,

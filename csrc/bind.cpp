@@ -6,10 +6,17 @@
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "bert_pytorch_amd gfx950 HIP kernels";
   m.def("ln_fwd", &bpa::ln_fwd, "fused LayerNorm forward");
-  m.def("ln_bwd", &bpa::ln_bwd, "fused LayerNorm backward");
+  // *_acc / acc: an existing gradient the result is added into in place;
+  // that output then comes back as None
+  m.def("ln_bwd", &bpa::ln_bwd, "fused LayerNorm backward", py::arg("dy"),
+        py::arg("x"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
+        py::arg("dgamma_acc") = py::none(), py::arg("dbeta_acc") = py::none());
   m.def("bias_gelu_fwd", &bpa::bias_gelu_fwd);
-  m.def("bias_gelu_bwd", &bpa::bias_gelu_bwd);
-  m.def("col_sum", &bpa::col_sum, "column sum [rows,H] -> fp32 [H]");
+  m.def("bias_gelu_bwd", &bpa::bias_gelu_bwd, py::arg("dy"), py::arg("x"),
+        py::arg("bias"), py::arg("dbias_acc") = py::none());
+  m.def("col_sum", &bpa::col_sum, "column sum [rows,H] -> fp32 [H]",
+        py::arg("x"), py::arg("acc") = py::none(),
+        py::arg("round_to") = py::none());
   m.def("gemm_bias_gelu_fwd", &bpa::gemm_bias_gelu_fwd,
         "hipblaslt GEMM with fused bias+GELU epilogue (+aux)");
   m.def("gemm_dgelu_bgrad", &bpa::gemm_dgelu_bgrad,
@@ -19,7 +26,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bias_dropout_residual_ln_bwd", &bpa::bias_dropout_residual_ln_bwd,
         py::arg("dy"), py::arg("z"), py::arg("mask"), py::arg("gamma"),
         py::arg("mean"), py::arg("rstd"), py::arg("p"), py::arg("has_bias"),
-        py::arg("dy2") = py::none());
+        py::arg("dy2") = py::none(), py::arg("dgamma_acc") = py::none(),
+        py::arg("dbeta_acc") = py::none(), py::arg("dbias_acc") = py::none());
   m.def("embedding_ln_dropout_fwd", &bpa::embedding_ln_dropout_fwd);
   m.def("embedding_ln_dropout_bwd", &bpa::embedding_ln_dropout_bwd);
   m.def("ce_fwd", &bpa::ce_fwd);
@@ -35,7 +43,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[T_pad,H] -> [B*S,H]: inverse of pack_rows, dropped rows zero");
   m.def("tr16_probe", &bpa::tr16_probe);
   m.def("wgrad_tn", &bpa::wgrad_tn, py::arg("dy"), py::arg("x"),
-        py::arg("splitk_override") = 0);
+        py::arg("splitk_override") = 0, py::arg("acc") = py::none());
   m.def("wgrad_tn_supported", &bpa::wgrad_tn_supported);
   m.def("mlm_head_fwd", &bpa::mlm_head_fwd,
         "MFMA MLM-decoder GEMM with fused bias + CE-forward epilogue");

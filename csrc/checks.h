@@ -69,4 +69,23 @@ inline void check_param(const char* op, const char* name,
               " elements, got ", t.sizes());
 }
 
+// fp32 gradient buffer of length H that a backward entry point adds its
+// column sums into; `like` is a tensor of the launch (device)
+inline void check_accum_dst(const char* op, const char* name,
+                            const torch::Tensor& t, const torch::Tensor& like,
+                            int64_t H) {
+  TORCH_CHECK(t.device() == like.device(), op, ": ", name, " device ",
+              t.device(), " does not match ", like.device());
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, op, ": ", name, " dtype ",
+              t.scalar_type(), " must be ", torch::kFloat32);
+  TORCH_CHECK(t.dim() == 1 && t.numel() == H && t.is_contiguous(), op, ": ",
+              name, " must be contiguous [", H, "], got ", t.sizes());
+}
+
+inline void check_accum_dst(const char* op, const char* name,
+                            const c10::optional<torch::Tensor>& t,
+                            const torch::Tensor& like, int64_t H) {
+  if (t.has_value()) check_accum_dst(op, name, *t, like, H);
+}
+
 }  // namespace bpa

@@ -32,14 +32,26 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor gamma,
                                   torch::Tensor beta, double eps);
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x,
                                   torch::Tensor gamma, torch::Tensor mean,
-                                  torch::Tensor rstd);
+                                  torch::Tensor rstd,
+                                  c10::optional<torch::Tensor> dgamma_acc,
+                                  c10::optional<torch::Tensor> dbeta_acc);
 torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor bias);
 std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
-                                         torch::Tensor bias);
-torch::Tensor col_sum(torch::Tensor x);
+                                         torch::Tensor bias,
+                                         c10::optional<torch::Tensor> dbias_acc);
+// `acc` (fp32 [H]): acc += round_to(column sum), nothing is returned
+torch::Tensor col_sum(
+    torch::Tensor x, c10::optional<torch::Tensor> acc = c10::nullopt,
+    c10::optional<torch::ScalarType> round_to = c10::nullopt);
 // layernorm.hip, shared by the backward entry points: fold [nparts, S]
-// fp32 partials over rows in a fixed order
-torch::Tensor col_reduce_full(torch::Tensor parts);
+// fp32 partials over rows in a fixed order. `dsts` cuts the [S] result
+// into dsts.size() equal segments; a segment with a destination (fp32) is
+// added to it, after rounding through `round_to` if that is a 16-bit type,
+// and its part of the returned tensor is then undefined.
+torch::Tensor col_reduce_full(
+    torch::Tensor parts,
+    const std::vector<c10::optional<torch::Tensor>>& dsts = {},
+    c10::optional<torch::ScalarType> round_to = c10::nullopt);
 std::vector<torch::Tensor> gemm_bias_gelu_fwd(torch::Tensor x,
                                               torch::Tensor w1,
                                               torch::Tensor b1);
@@ -54,7 +66,9 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
 std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
     torch::Tensor dy, torch::Tensor z, torch::Tensor mask, torch::Tensor gamma,
     torch::Tensor mean, torch::Tensor rstd, double p, bool has_bias,
-    c10::optional<torch::Tensor> dy2);
+    c10::optional<torch::Tensor> dy2, c10::optional<torch::Tensor> dgamma_acc,
+    c10::optional<torch::Tensor> dbeta_acc,
+    c10::optional<torch::Tensor> dbias_acc);
 std::vector<torch::Tensor> embedding_ln_dropout_fwd(
     torch::Tensor ids, c10::optional<torch::Tensor> tt, torch::Tensor word,
     torch::Tensor pos, c10::optional<torch::Tensor> tok, torch::Tensor gamma,
@@ -75,8 +89,10 @@ std::vector<torch::Tensor> attention_fwd(torch::Tensor qkv,
                                          int64_t num_heads, double p,
                                          int64_t seed, int64_t offset);
 torch::Tensor tr16_probe(int64_t addr_mode);
+// `acc` ([M, N], dy's dtype): acc += dW in place, nothing is returned
 torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x,
-                       int64_t splitk_override);
+                       int64_t splitk_override,
+                       c10::optional<torch::Tensor> acc);
 std::vector<torch::Tensor> mlm_head_fwd(torch::Tensor h, torch::Tensor w,
                                         torch::Tensor bias,
                                         torch::Tensor labels,

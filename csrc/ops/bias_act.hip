@@ -156,13 +156,17 @@ torch::Tensor bias_gelu_fwd(torch::Tensor x, torch::Tensor bias) {
   return y;
 }
 
-std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
-                                         torch::Tensor bias) {
+std::vector<torch::Tensor> bias_gelu_bwd(
+    torch::Tensor dy, torch::Tensor x, torch::Tensor bias,
+    c10::optional<torch::Tensor> dbias_acc) {
   check_rows_2d("bias_gelu_bwd", "x", x);
   check_like("bias_gelu_bwd", "dy", dy, "x", x);
   const int64_t rows = x.size(0);
   const int H = x.size(1);
   check_param("bias_gelu_bwd", "bias", bias, H);
+  check_accum_dst("bias_gelu_bwd", "dbias_acc", dbias_acc, x, H);
+  TORCH_CHECK(!dbias_acc.has_value() || bias.scalar_type() == torch::kFloat32,
+              "bias_gelu_bwd: an accumulating output needs fp32 bias");
   auto bias_f = bias.contiguous().to(torch::kFloat32);
   auto dx = torch::empty_like(x);
   auto fopts = x.options().dtype(torch::kFloat32);
@@ -183,18 +187,25 @@ std::vector<torch::Tensor> bias_gelu_bwd(torch::Tensor dy, torch::Tensor x,
                        dptr<scalar_t>(x), bias_f.data_ptr<float>(),
                        dptr<scalar_t>(dx), part.data_ptr<float>(),
                        static_cast<int>(rows), H, rows_per_block);
-    dbias = col_reduce_full(part);
+    dbias = dbias_acc.has_value() ? col_reduce_full(part, {dbias_acc})
+                                  : col_reduce_full(part);
   });
+  // added into dbias_acc: nothing to hand back
+  if (dbias_acc.has_value()) return {dx, torch::Tensor()};
   if (bias.scalar_type() != torch::kFloat32) {
     return {dx, dbias.to(bias.scalar_type())};
   }
   return {dx, dbias};
 }
 
-torch::Tensor col_sum(torch::Tensor x) {
+torch::Tensor col_sum(torch::Tensor x, c10::optional<torch::Tensor> acc,
+                      c10::optional<torch::ScalarType> round_to) {
   TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), "col_sum: bad x");
   const int rows = x.size(0);
   const int H = x.size(1);
+  check_accum_dst("col_sum", "acc", acc, x, H);
+  TORCH_CHECK(acc.has_value() || !round_to.has_value(),
+              "col_sum: round_to goes with acc");
   const int rows_per_chunk = 32;
   const int n_chunks = (rows + rows_per_chunk - 1) / rows_per_chunk;
   auto fopts = x.options().dtype(torch::kFloat32);
@@ -209,9 +220,10 @@ torch::Tensor col_sum(torch::Tensor x) {
     hipLaunchKernelGGL((col_sum_partial_kernel<scalar_t, kVec>), grid,
                        dim3(threads), 0, stream, dptr<scalar_t>(x),
                        part.data_ptr<float>(), rows, H, rows_per_chunk);
-    out = col_reduce_full(part);
+    out = acc.has_value() ? col_reduce_full(part, {acc}, round_to)
+                          : col_reduce_full(part);
   });
-  return out;
+  return acc.has_value() ? torch::Tensor() : out;
 }
 
 }  // namespace bpa

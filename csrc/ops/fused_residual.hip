@@ -124,7 +124,9 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_fwd(
 std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
     torch::Tensor dy, torch::Tensor z, torch::Tensor mask, torch::Tensor gamma,
     torch::Tensor mean, torch::Tensor rstd, double p, bool has_bias,
-    c10::optional<torch::Tensor> dy2) {
+    c10::optional<torch::Tensor> dy2, c10::optional<torch::Tensor> dgamma_acc,
+    c10::optional<torch::Tensor> dbeta_acc,
+    c10::optional<torch::Tensor> dbias_acc) {
   check_rows_2d("bdrl_bwd", "z", z);
   check_like("bdrl_bwd", "dy", dy, "z", z);
   if (dy2.has_value()) {
@@ -137,6 +139,16 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
   check_row_stat("bdrl_bwd", "rstd", rstd, rows);
   check_param("bdrl_bwd", "gamma", gamma, H);
   if (p > 0.0) check_drop_mask("bdrl_bwd", mask, rows, H);
+  check_accum_dst("bdrl_bwd", "dgamma_acc", dgamma_acc, z, H);
+  check_accum_dst("bdrl_bwd", "dbeta_acc", dbeta_acc, z, H);
+  check_accum_dst("bdrl_bwd", "dbias_acc", dbias_acc, z, H);
+  // a gradient with a destination is added there and comes back undefined
+  const bool fused = dgamma_acc.has_value() || dbeta_acc.has_value() ||
+                     dbias_acc.has_value();
+  TORCH_CHECK(!fused || gamma.scalar_type() == torch::kFloat32,
+              "bdrl_bwd: accumulating outputs need fp32 parameters");
+  TORCH_CHECK(!dbias_acc.has_value() || has_bias,
+              "bdrl_bwd: dbias_acc without a bias");
   auto gamma_f = gamma.contiguous().to(torch::kFloat32);
   auto dx = torch::empty_like(z);
   auto dz_res = torch::empty_like(z);
@@ -149,11 +161,20 @@ std::vector<torch::Tensor> bias_dropout_residual_ln_bwd(
         "bdrl_bwd", dy, dy2.has_value() ? *dy2 : torch::Tensor(), z, mask,
         gamma_f, mean, rstd, dx, dz_res, p, has_bias, stream);
   });
-  auto out = col_reduce_full(part);
-  auto dgamma = out.narrow(0, 0, H).contiguous();
-  auto dbeta = out.narrow(0, H, H).contiguous();
-  auto dbias =
-      has_bias ? out.narrow(0, 2 * H, H).contiguous() : torch::empty({0}, fopts);
+  torch::Tensor out;
+  if (fused) {
+    // the partials are [nblocks, 3H] with a bias and [nblocks, 2H] without
+    std::vector<c10::optional<torch::Tensor>> dsts = {dgamma_acc, dbeta_acc};
+    if (has_bias) dsts.push_back(dbias_acc);
+    out = col_reduce_full(part, dsts);
+  } else {
+    out = col_reduce_full(part);
+  }
+  auto dgamma = dgamma_acc.has_value() ? torch::Tensor() : out.narrow(0, 0, H);
+  auto dbeta = dbeta_acc.has_value() ? torch::Tensor() : out.narrow(0, H, H);
+  auto dbias = !has_bias              ? torch::empty({0}, fopts)
+               : dbias_acc.has_value() ? torch::Tensor()
+                                       : out.narrow(0, 2 * H, H);
   if (gamma.scalar_type() != torch::kFloat32) {
     dgamma = dgamma.to(gamma.scalar_type());
     dbeta = dbeta.to(gamma.scalar_type());

@@ -95,13 +95,49 @@ __device__ __forceinline__ void strip_sum(const float* __restrict__ m, int r0,
   }
 }
 
+// Where the fold's result goes. The [S] result is cut into S / seg
+// segments of seg columns (dgamma | dbeta | dbias, ...); a segment with a
+// destination is ADDED to it, dst[c] = dst[c] + round(sum), the fp32 add
+// autograd's gradient accumulation would make on the stored result, and a
+// segment without one is stored to out. round: 0 keeps the fp32 sum, 1 / 2
+// round it through bf16 / fp16 first (a gradient that reaches its fp32
+// parameter through a 16-bit cast). seg is a multiple of 4 whenever a
+// destination is set, so a thread's 4 columns share one segment.
+struct FoldDst {
+  float* d0;
+  float* d1;
+  float* d2;
+  int seg;
+  int round;
+};
+
+__device__ __forceinline__ float fold_round(float v, int round) {
+  if (round == 1) return __bfloat162float(__float2bfloat16(v));
+  if (round == 2) return __half2float(__float2half(v));
+  return v;
+}
+
+__device__ __forceinline__ void fold_store(const FoldDst& fd, float* out,
+                                           int c, int nk,
+                                           const float (&sum)[4]) {
+  const int s = c / fd.seg;
+  float* d = s == 0 ? fd.d0 : s == 1 ? fd.d1 : s == 2 ? fd.d2 : nullptr;
+  if (d != nullptr) {
+    d += c - s * fd.seg;
+    for (int k = 0; k < nk; ++k) d[k] = d[k] + fold_round(sum[k], fd.round);
+  } else {
+    for (int k = 0; k < nk; ++k) out[c + k] = sum[k];
+  }
+}
+
 // Deterministic blocked column reduce: out[j][c] = sum over the j-th
 // contiguous row block of parts[p][c]. Each thread owns 4 consecutive
 // fp32 columns (one uint4 per row) and adds its rows in order. Direct
 // store: no atomics, no zero-fill.
 __global__ void col_reduce_blocked_kernel(const float* __restrict__ parts,
                                           int nparts, int S, int rows_per_j,
-                                          float* __restrict__ out) {
+                                          float* __restrict__ out,
+                                          FoldDst fd) {
   const int c = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (c >= S) return;
   const int p0 = blockIdx.y * rows_per_j;
@@ -109,8 +145,7 @@ __global__ void col_reduce_blocked_kernel(const float* __restrict__ parts,
   const int nk = min(4, S - c);
   float acc[4] = {};
   strip_sum(parts, p0, p1, S, c, nk, acc);
-  float* dst = out + static_cast<int64_t>(blockIdx.y) * S + c;
-  for (int k = 0; k < nk; ++k) dst[k] = acc[k];
+  fold_store(fd, out + static_cast<int64_t>(blockIdx.y) * S, c, nk, acc);
 }
 
 // One-launch variant for many partial rows: `chunk` rows per y-block,
@@ -124,7 +159,8 @@ __global__ void col_reduce_ordered_kernel(const float* __restrict__ parts,
                                           int nparts, int S, int chunk,
                                           float* __restrict__ tmp,
                                           unsigned int* __restrict__ counters,
-                                          float* __restrict__ out) {
+                                          float* __restrict__ out,
+                                          FoldDst fd) {
   const int c = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const bool active = c < S;
   const int nk = min(4, S - c);
@@ -150,7 +186,7 @@ __global__ void col_reduce_ordered_kernel(const float* __restrict__ parts,
   // strip_sum see every block's stores.
   float sum[4] = {};
   strip_sum(tmp, 0, static_cast<int>(gridDim.y), S, c, nk, sum);
-  for (int k = 0; k < nk; ++k) out[c + k] = sum[k];
+  fold_store(fd, out, c, nk, sum);
 }
 
 // partial rows per y-block of col_reduce_ordered_kernel: measured best of
@@ -158,21 +194,42 @@ __global__ void col_reduce_ordered_kernel(const float* __restrict__ parts,
 // chunks cost parallelism in the first phase)
 constexpr int kColChunk = 32;
 
-torch::Tensor col_reduce_full(torch::Tensor parts) {
+torch::Tensor col_reduce_full(torch::Tensor parts,
+                              const std::vector<c10::optional<torch::Tensor>>& dsts,
+                              c10::optional<torch::ScalarType> round_to) {
   const int nparts = parts.size(0);
   const int S = parts.size(1);
+  FoldDst fd{nullptr, nullptr, nullptr, S > 0 ? S : 1, 0};
+  if (!dsts.empty()) {
+    const int nseg = static_cast<int>(dsts.size());
+    TORCH_CHECK(nseg <= 3 && S % nseg == 0 && (S / nseg) % 4 == 0,
+                "col_reduce_full: ", nseg, " destinations do not cut ", S,
+                " columns into segments of a multiple of 4");
+    fd.seg = S / nseg;
+    float** slot[3] = {&fd.d0, &fd.d1, &fd.d2};
+    for (int i = 0; i < nseg; ++i) {
+      if (!dsts[i].has_value()) continue;
+      check_accum_dst("col_reduce_full", "destination", *dsts[i], parts,
+                      fd.seg);
+      *slot[i] = dsts[i]->data_ptr<float>();
+    }
+    if (round_to.has_value() && *round_to != torch::kFloat32) {
+      TORCH_CHECK(*round_to == torch::kBFloat16 || *round_to == torch::kHalf,
+                  "col_reduce_full: cannot round through ", *round_to);
+      fd.round = *round_to == torch::kBFloat16 ? 1 : 2;
+    }
+  }
   auto stream = at::hip::getCurrentHIPStream();
   const int xblocks = (S / 4 + 255) / 256;
+  auto out = torch::empty({S}, parts.options());
   if (nparts <= 48) {
-    auto out = torch::empty({S}, parts.options());
     hipLaunchKernelGGL(col_reduce_blocked_kernel, dim3(xblocks, 1),
                        dim3(256), 0, stream, parts.data_ptr<float>(), nparts,
-                       S, nparts, out.data_ptr<float>());
+                       S, nparts, out.data_ptr<float>(), fd);
     return out;
   }
   const int chunk = kColChunk;
   const int yblocks = (nparts + chunk - 1) / chunk;
-  auto out = torch::empty({S}, parts.options());
   auto tmp = torch::empty({yblocks, S}, parts.options());
   auto counters = torch::zeros({xblocks}, parts.options().dtype(torch::kInt32));
   dim3 grid(xblocks, yblocks);
@@ -180,7 +237,7 @@ torch::Tensor col_reduce_full(torch::Tensor parts) {
                      parts.data_ptr<float>(), nparts, S, chunk,
                      tmp.data_ptr<float>(),
                      reinterpret_cast<unsigned int*>(counters.data_ptr<int>()),
-                     out.data_ptr<float>());
+                     out.data_ptr<float>(), fd);
   return out;
 }
 
@@ -211,13 +268,21 @@ std::vector<torch::Tensor> ln_fwd(torch::Tensor x, torch::Tensor gamma,
 
 std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x,
                                   torch::Tensor gamma, torch::Tensor mean,
-                                  torch::Tensor rstd) {
+                                  torch::Tensor rstd,
+                                  c10::optional<torch::Tensor> dgamma_acc,
+                                  c10::optional<torch::Tensor> dbeta_acc) {
   check_rows_2d("ln_bwd", "x", x);
   check_like("ln_bwd", "dy", dy, "x", x);
   const int rows = x.size(0), H = x.size(1);
   check_row_stat("ln_bwd", "mean", mean, rows);
   check_row_stat("ln_bwd", "rstd", rstd, rows);
   check_param("ln_bwd", "gamma", gamma, H);
+  check_accum_dst("ln_bwd", "dgamma_acc", dgamma_acc, x, H);
+  check_accum_dst("ln_bwd", "dbeta_acc", dbeta_acc, x, H);
+  // a gradient with a destination is added there and comes back undefined
+  const bool fused = dgamma_acc.has_value() || dbeta_acc.has_value();
+  TORCH_CHECK(!fused || gamma.scalar_type() == torch::kFloat32,
+              "ln_bwd: accumulating outputs need fp32 gamma");
   auto gamma_f = gamma.contiguous().to(torch::kFloat32);
   auto dx = torch::empty_like(x);
   auto stream = at::hip::getCurrentHIPStream();
@@ -228,13 +293,14 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor x,
                                               gamma_f, mean, rstd, dx, none,
                                               0.0, false, stream);
   });
-  auto dgb = col_reduce_full(part);
-  auto dgamma = dgb.narrow(0, 0, H);
-  auto dbeta = dgb.narrow(0, H, H);
+  auto dgb = fused ? col_reduce_full(part, {dgamma_acc, dbeta_acc})
+                   : col_reduce_full(part);
+  auto dgamma = dgamma_acc.has_value() ? torch::Tensor() : dgb.narrow(0, 0, H);
+  auto dbeta = dbeta_acc.has_value() ? torch::Tensor() : dgb.narrow(0, H, H);
   if (gamma.scalar_type() != torch::kFloat32) {
     return {dx, dgamma.to(gamma.scalar_type()), dbeta.to(gamma.scalar_type())};
   }
-  return {dx, dgamma.contiguous(), dbeta.contiguous()};
+  return {dx, dgamma, dbeta};
 }
 
 }  // namespace bpa

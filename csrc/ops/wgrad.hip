@@ -89,7 +89,11 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(
 // narrowing rounds to nearest-even; for fp16 a sum beyond +-65504
 // becomes +-inf, never a clamped finite value (the GradScaler's
 // overflow detection depends on it).
-template <typename T>
+// ACC: out holds a gradient already and gets out = T(float(out) +
+// float(T(sum))). The inner rounding to T is the one the plain store makes
+// and the outer one is a 16-bit tensor add's, so the result is bit for bit
+// that of adding the stored dW to out afterwards.
+template <typename T, bool ACC>
 __global__ void wgrad_combine_kernel(const float* __restrict__ part,
                                      T* __restrict__ out, int splitk,
                                      int64_t mn) {
@@ -107,6 +111,13 @@ __global__ void wgrad_combine_kernel(const float* __restrict__ part,
   T o[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) o[k] = Tr::from_f32(s[k]);
+  if (ACC) {
+    T a[4];
+    *reinterpret_cast<uint2*>(a) = *reinterpret_cast<const uint2*>(out + i);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      o[k] = Tr::from_f32(Tr::to_f32(a[k]) + Tr::to_f32(o[k]));
+  }
   *reinterpret_cast<uint2*>(out + i) = *reinterpret_cast<uint2*>(o);
 }
 
@@ -126,7 +137,8 @@ bool wgrad_tn_profitable(int64_t K, int64_t M, int64_t N) {
 
 template <typename T>
 static torch::Tensor wgrad_tn_t(torch::Tensor dy, torch::Tensor x,
-                                int64_t splitk_override) {
+                                int64_t splitk_override,
+                                const c10::optional<torch::Tensor>& acc) {
   const int K = dy.size(0), M = dy.size(1), N = x.size(1);
   TORCH_CHECK(x.size(0) == K, "wgrad_tn: K mismatch");
   TORCH_CHECK(wgrad_tn_supported(K, M, N), "wgrad_tn: unsupported shape");
@@ -150,7 +162,10 @@ static torch::Tensor wgrad_tn_t(torch::Tensor dy, torch::Tensor x,
 
   auto part = torch::empty({splitk, static_cast<int64_t>(M), N},
                            dy.options().dtype(torch::kFloat32));
-  auto out = torch::empty({static_cast<int64_t>(M), N}, dy.options());
+  // with acc the combine adds into it and nothing is returned
+  auto out = acc.has_value()
+                 ? *acc
+                 : torch::empty({static_cast<int64_t>(M), N}, dy.options());
   auto stream = at::hip::getCurrentHIPStream();
   dim3 grid(M / wg::kBM, N / wg::kBN, splitk), block(256);
   // two double-buffered [bk][kStride] images (dy, x)
@@ -169,16 +184,25 @@ static torch::Tensor wgrad_tn_t(torch::Tensor dy, torch::Tensor x,
   else
     launch(&wgrad_tn_kernel<T, 32>);
   const int64_t mn = static_cast<int64_t>(M) * N;
-  hipLaunchKernelGGL(wgrad_combine_kernel<T>, dim3((mn / 4 + 255) / 256),
-                     dim3(256), 0, stream, part.data_ptr<float>(),
+  const dim3 cgrid((mn / 4 + 255) / 256);
+  if (acc.has_value()) {
+    hipLaunchKernelGGL((wgrad_combine_kernel<T, true>), cgrid, dim3(256), 0,
+                       stream, part.data_ptr<float>(),
+                       reinterpret_cast<T*>(out.data_ptr()), splitk, mn);
+    return torch::Tensor();
+  }
+  hipLaunchKernelGGL((wgrad_combine_kernel<T, false>), cgrid, dim3(256), 0,
+                     stream, part.data_ptr<float>(),
                      reinterpret_cast<T*>(out.data_ptr()), splitk, mn);
   return out;
 }
 
 // dW = dy^T @ x; dy [K,M] row-major contiguous, x [K,N] likewise, both
-// bf16 or both fp16; dW comes back in the same dtype.
+// bf16 or both fp16; dW comes back in the same dtype, or, with `acc`
+// ([M, N] contiguous, same dtype and device), is added to acc in place.
 torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x,
-                       int64_t splitk_override) {
+                       int64_t splitk_override,
+                       c10::optional<torch::Tensor> acc) {
   const auto dt = dy.scalar_type();
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 2 && dy.is_contiguous() &&
                   (dt == torch::kBFloat16 || dt == torch::kHalf),
@@ -187,8 +211,19 @@ torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x,
               "wgrad_tn: x must be contiguous 2D");
   TORCH_CHECK(x.scalar_type() == dt, "wgrad_tn: x dtype ", x.scalar_type(),
               " does not match dy dtype ", dt);
-  if (dt == torch::kHalf) return wgrad_tn_t<_Float16>(dy, x, splitk_override);
-  return wgrad_tn_t<__bf16>(dy, x, splitk_override);
+  if (acc.has_value()) {
+    TORCH_CHECK(acc->device() == dy.device(), "wgrad_tn: acc device ",
+                acc->device(), " does not match dy device ", dy.device());
+    TORCH_CHECK(acc->scalar_type() == dt, "wgrad_tn: acc dtype ",
+                acc->scalar_type(), " does not match dy dtype ", dt);
+    TORCH_CHECK(acc->dim() == 2 && acc->size(0) == dy.size(1) &&
+                    acc->size(1) == x.size(1) && acc->is_contiguous(),
+                "wgrad_tn: acc must be contiguous [", dy.size(1), ", ",
+                x.size(1), "], got ", acc->sizes());
+  }
+  if (dt == torch::kHalf)
+    return wgrad_tn_t<_Float16>(dy, x, splitk_override, acc);
+  return wgrad_tn_t<__bf16>(dy, x, splitk_override, acc);
 }
 
 }  // namespace bpa
