@@ -9,7 +9,10 @@ Re-designed from the reference's ``ShardedPretrainingDataset``
   sequentially;
 * RoBERTa-style dynamic masking (80/10/10) computed on CPU workers from
   the new {input_ids, special_token_positions, next_sentence_labels}
-  schema, plus the legacy NVIDIA pre-masked schema;
+  schema, plus the legacy NVIDIA pre-masked schema; ``static_masking``
+  instead draws the mask of sample ``idx`` from a generator seeded by
+  ``(seed, idx)``, so a held-out set is the same tensors at every
+  evaluation, in every run, at any worker count;
 * a rank-chunked sequential sampler whose position checkpoints into the
   training state dict.
 
@@ -47,6 +50,7 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         random_token_prob: float = 0.1,
         shuffle: bool = False,
         seed: Optional[int] = None,
+        static_masking: bool = False,
     ):
         if original_token_prob + random_token_prob > 1:
             raise ValueError("original_token_prob + random_token_prob > 1")
@@ -66,6 +70,7 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         self.original_token_prob = original_token_prob
         self.random_token_prob = random_token_prob
         self.seed = seed
+        self.static_masking = static_masking
         self.epoch = 0
         self._rng = np.random.default_rng(seed)
 
@@ -83,6 +88,16 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
 
     def __len__(self) -> int:
         return self.file_idxs[-1][1]
+
+    def rewind(self) -> None:
+        """Forget the resident shard so the next read may start at any
+        sample again (a held-out set is re-read from its first sample at
+        every evaluation; reads stay sequential from there on)."""
+        if self._next_thread is not None:
+            self._next_thread.join()
+        self.data = self._next_data = self._next_thread = None
+        self.file_idx = self.next_file_idx = None
+        self.file_sample_start_idx = self.file_sample_end_idx = -1
 
     def __getitem__(self, idx: int) -> List[np.ndarray]:
         if self.data is None:
@@ -116,8 +131,15 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
             special = self.data["special_token_positions"][local]
             segment_ids = self._segment_ids(input_ids, special)
             input_mask = self._input_mask(input_ids, special)
+            # static: a generator of this sample's own, whatever was read
+            # before it and whichever worker reads it; the stream stays put
+            rng = (
+                np.random.default_rng([self.seed or 0, idx])
+                if self.static_masking
+                else self._rng
+            )
             masked_input_ids, masked_lm_labels = self._mask_input(
-                input_ids, special
+                input_ids, special, rng
             )
         else:  # legacy NVIDIA pre-masked format
             segment_ids = self.data["segment_ids"][local]
@@ -168,9 +190,13 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         return input_mask
 
     def _mask_input(
-        self, input_ids: np.ndarray, special: np.ndarray
+        self,
+        input_ids: np.ndarray,
+        special: np.ndarray,
+        rng: np.random.Generator,
     ) -> Tuple[np.ndarray, np.ndarray]:
-        """Dynamic 80/10/10 masking over non-special, non-pad positions."""
+        """80/10/10 masking over non-special, non-pad positions, drawn
+        from ``rng``."""
         input_ids = input_ids.copy()  # never mutate the cached shard
         masked_lm_labels = np.full_like(input_ids, -1)
         special_set = set(int(s) for s in special)
@@ -184,14 +210,14 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
             self.max_pred_per_seq,
             max(1, int(candidates.size * self.masked_lm_prob)),
         )
-        mask_indices = self._rng.choice(candidates, mask_count, replace=False)
+        mask_indices = rng.choice(candidates, mask_count, replace=False)
         masked_lm_labels[mask_indices] = input_ids[mask_indices]
-        draws = self._rng.random(mask_count)
+        draws = rng.random(mask_count)
         for idx, draw in zip(mask_indices, draws):
             if draw < self.original_token_prob:
                 continue  # keep original token
             if draw < self.original_token_prob + self.random_token_prob:
-                input_ids[idx] = self._rng.integers(0, self.vocab_size - 1)
+                input_ids[idx] = rng.integers(0, self.vocab_size - 1)
             else:
                 input_ids[idx] = self.mask_token_index
         return input_ids, masked_lm_labels

@@ -586,6 +586,11 @@ class BertForPreTraining(BertPreTrainedModel):
     default; the in-repo fused MFMA kernel with BPA_FUSED_MLM=1), and
     ``BertPretrainingCriterion`` detects the 0-dim tensor and adds only
     the NSP term.
+
+    With ``mlm_eval=True`` (held-out evaluation, evaluation.py) the first
+    return element is instead the ``ops.MlmEval`` tuple (loss_sum, count,
+    correct, pred) of ``ops.mlm_decoder_eval``: no [P, V] scores, no
+    autograd graph.
     """
 
     def __init__(self, config: BertConfig):
@@ -610,6 +615,7 @@ class BertForPreTraining(BertPreTrainedModel):
         masked_lm_labels=None,
         max_predictions_per_seq=None,
         compute_mlm_loss=False,
+        mlm_eval=False,
     ):
         encoded, pooled = self.bert(input_ids, token_type_ids, attention_mask)
         sequence_output = encoded[-1] if isinstance(encoded, list) else encoded
@@ -649,7 +655,15 @@ class BertForPreTraining(BertPreTrainedModel):
             gathered_labels = flat_labels.index_select(0, positions)
         hidden = sequence_output.reshape(-1, sequence_output.shape[-1])
         masked_hidden = hidden.index_select(0, positions)
-        if compute_mlm_loss:
+        if mlm_eval:
+            head = self.cls.predictions
+            scores = ops.mlm_decoder_eval(
+                head.transform(masked_hidden),
+                head.decoder.weight,
+                head.bias,
+                gathered_labels,
+            )
+        elif compute_mlm_loss:
             # fused decoder-GEMM + bias + CE path (ops/mlm.py): the
             # first return element is the scalar MLM loss instead of
             # the [P, V] scores; BertPretrainingCriterion detects the

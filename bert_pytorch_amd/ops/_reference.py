@@ -183,3 +183,21 @@ def cross_entropy(
     return F.cross_entropy(
         logits.float(), labels, ignore_index=ignore_index, reduction="mean"
     )
+
+
+def mlm_eval(
+    logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -1
+) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(loss_sum, count, correct, pred) of [P, V] logits against labels.
+
+    fp32 throughout; ``pred`` is int32 and, on a tie, the lowest column
+    that attains the row maximum.
+    """
+    x = logits.float()
+    valid = labels != ignore_index
+    lse = torch.logsumexp(x, dim=1)
+    picked = x.gather(1, labels.clamp(min=0).unsqueeze(1)).squeeze(1)
+    loss_sum = torch.where(valid, lse - picked, torch.zeros_like(lse)).sum()
+    pred = torch.argmax(x, dim=1)
+    correct = ((pred == labels) & valid).sum()
+    return loss_sum, valid.sum().float(), correct.float(), pred.to(torch.int32)

@@ -36,11 +36,18 @@ The kernel is instantiated for bf16 and fp16: the fused path runs in
 the hidden states' 16-bit dtype, or in the autocast GPU dtype when
 they are fp32, and the logits are materialized in that dtype (fp16:
 tests/test_gpu_fp16_kernels.py::test_mlm_*).
+
+Evaluation (``mlm_decoder_eval``) runs the kernel's logits-free
+instantiation ``mlm_head_eval``: the same GEMM and statistics, no [P, V]
+store, plus the top-1 prediction and the number of correct rows from
+the same epilogue (docs/KERNELS.md "MLM head, evaluation
+instantiation"; tests/test_gpu_mlm_eval.py).
 """
 
 from __future__ import annotations
 
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn.functional as F
@@ -150,3 +157,63 @@ def mlm_decoder_loss(
     # CPU / eager oracle
     scores = F.linear(hidden.float(), weight.float(), bias.float())
     return _reference.cross_entropy(scores, labels, ignore_index)
+
+
+class MlmEval(NamedTuple):
+    """Held-out MLM statistics of one batch, all on ``hidden``'s device."""
+
+    loss_sum: torch.Tensor  # f32 []: summed NLL over non-ignored rows
+    count: torch.Tensor  # f32 []: non-ignored rows
+    correct: torch.Tensor  # f32 []: non-ignored rows with pred == label
+    pred: torch.Tensor  # int32 [P]: top-1 column (lowest index on a tie)
+
+
+@torch.no_grad()
+def mlm_decoder_eval(
+    hidden: torch.Tensor,
+    weight: torch.Tensor,
+    bias: torch.Tensor,
+    labels: torch.Tensor,
+    ignore_index: int = -1,
+) -> MlmEval:
+    """Loss sum, row count, correct count and top-1 prediction of
+    ``hidden @ weight.T + bias`` against ``labels``; no host sync, no
+    autograd graph. Routed like ``mlm_decoder_loss``: the fused kernel's
+    evaluation instantiation where the fused training kernel would run,
+    else library GEMM + ``ce_fwd`` + ``argmax`` on the GPU, else the fp32
+    reference.
+    """
+    if use_native(hidden):
+        ext = extension()
+        P, K = hidden.shape
+        V = weight.shape[0]
+        pad = (-P) % _TILE
+        dtype = _kernel_dtype(hidden)
+        if (
+            dtype is not None
+            and ext.mlm_head_supported(P + pad, V, K)
+            and os.environ.get("BPA_FUSED_MLM") != "0"
+        ):
+            h = hidden.to(dtype)
+            lab = labels
+            if pad:
+                h = torch.cat([h, h.new_zeros(pad, K)])
+                lab = torch.cat([lab, lab.new_full((pad,), ignore_index)])
+            loss_sum, count, correct, _lse, pred = ext.mlm_head_eval(
+                h.contiguous(),
+                weight.to(dtype).contiguous(),
+                bias.float().contiguous(),
+                lab,
+                ignore_index,
+            )
+            return MlmEval(loss_sum, count, correct, pred[:P])
+        w, b = weight, bias
+        if not torch.is_autocast_enabled():
+            w, b = w.to(hidden.dtype), b.to(hidden.dtype)
+        scores = F.linear(hidden, w, b).contiguous()
+        loss_sum, count, _lse = ext.ce_fwd(scores, labels, ignore_index)
+        pred = torch.argmax(scores, dim=1)
+        correct = ((pred == labels) & (labels != ignore_index)).sum()
+        return MlmEval(loss_sum, count, correct.float(), pred.to(torch.int32))
+    scores = F.linear(hidden.float(), weight.float(), bias.float())
+    return MlmEval(*_reference.mlm_eval(scores, labels, ignore_index))

@@ -47,6 +47,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_tn_supported", &bpa::wgrad_tn_supported);
   m.def("mlm_head_fwd", &bpa::mlm_head_fwd,
         "MFMA MLM-decoder GEMM with fused bias + CE-forward epilogue");
+  m.def("mlm_head_eval", &bpa::mlm_head_eval,
+        "mlm_head_fwd without the logits: loss/count/correct sums, lse, "
+        "top-1 prediction");
   m.def("mlm_head_supported", &bpa::mlm_head_supported);
   m.def("wgrad_tn_profitable", &bpa::wgrad_tn_profitable);
   m.def("kfac_factor_update", &bpa::kfac_factor_update,

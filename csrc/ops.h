@@ -97,6 +97,12 @@ std::vector<torch::Tensor> mlm_head_fwd(torch::Tensor h, torch::Tensor w,
                                         torch::Tensor bias,
                                         torch::Tensor labels,
                                         int64_t ignore_index);
+// logits-free evaluation instantiation of the same kernel:
+// {loss_sum, count, correct, lse [P], pred [P] i32}
+std::vector<torch::Tensor> mlm_head_eval(torch::Tensor h, torch::Tensor w,
+                                         torch::Tensor bias,
+                                         torch::Tensor labels,
+                                         int64_t ignore_index);
 bool mlm_head_supported(int64_t P, int64_t V, int64_t K);
 bool wgrad_tn_supported(int64_t K, int64_t M, int64_t N);
 bool wgrad_tn_profitable(int64_t K, int64_t M, int64_t N);

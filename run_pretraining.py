@@ -30,6 +30,7 @@ import torch
 
 from bert_pytorch_amd.config import BertConfig, merge_config_and_args
 from bert_pytorch_amd.data import DistributedSampler, ShardedPretrainingDataset
+from bert_pytorch_amd.evaluation import evaluate_pretraining, make_eval_loader
 from bert_pytorch_amd.models import BertForPreTraining, BertPretrainingCriterion
 from bert_pytorch_amd.optim import FusedLAMB, PolyWarmUpScheduler
 from bert_pytorch_amd.parallel import comm
@@ -104,6 +105,15 @@ def parse_arguments(args=None) -> argparse.Namespace:
     parser.add_argument("--kfac_factor_interval", type=int, default=1)
     parser.add_argument("--kfac_skip_layers", nargs="+",
                         default=["BertLMPredictionHead", "embedding"])
+    parser.add_argument("--eval_input_dir", type=str, default=None,
+                        help="directory tree of held-out *.hdf5 shards (either "
+                             "schema); enables evaluation, logged under the "
+                             "tag 'eval'")
+    parser.add_argument("--eval_interval", type=int, default=0,
+                        help="evaluate every N optimizer steps (0 = once, "
+                             "after the last step)")
+    parser.add_argument("--eval_batches", type=int, default=16,
+                        help="micro-batches per rank per evaluation")
     parser.add_argument("--profile", type=int, default=0,
                         help="profile N optimizer steps with torch.profiler "
                              "(chrome trace under output_dir/profile) and stop")
@@ -291,11 +301,7 @@ def _resume_step_of(resume_state) -> int:
     return 0
 
 
-def prepare_dataset(args, resume_state):
-    files = sorted(str(p) for p in Path(args.input_dir).rglob("*.hdf5"))
-    if not files:
-        raise RuntimeError(f"no *.hdf5 shards under {args.input_dir}")
-
+def _mask_index_and_vocab(args):
     mask_index = args.mask_token_index
     vocab_size = None
     if args.vocab_file and os.path.isfile(args.vocab_file):
@@ -311,6 +317,15 @@ def prepare_dataset(args, resume_state):
         # must stay < real vocab; reference: run_pretraining.py:370-388)
         model_cfg = BertConfig.from_json_file(args.model_config_file)
         vocab_size = model_cfg.vocab_size
+    return mask_index, vocab_size
+
+
+def prepare_dataset(args, resume_state):
+    files = sorted(str(p) for p in Path(args.input_dir).rglob("*.hdf5"))
+    if not files:
+        raise RuntimeError(f"no *.hdf5 shards under {args.input_dir}")
+
+    mask_index, vocab_size = _mask_index_and_vocab(args)
 
     dataset = ShardedPretrainingDataset(
         files,
@@ -336,6 +351,56 @@ def prepare_dataset(args, resume_state):
         persistent_workers=args.num_workers > 0,
     )
     return loader, sampler
+
+
+def prepare_eval_loader(args):
+    """Held-out set: chunked sampler at a fixed epoch, masks fixed by
+    (--seed, sample index), a loader with a generator of its own. The same
+    ``--eval_batches`` batches are read at every evaluation."""
+    files = sorted(str(p) for p in Path(args.eval_input_dir).rglob("*.hdf5"))
+    if not files:
+        raise RuntimeError(f"no *.hdf5 shards under {args.eval_input_dir}")
+    mask_index, vocab_size = _mask_index_and_vocab(args)
+    dataset = ShardedPretrainingDataset(
+        files,
+        mask_token_index=mask_index,
+        max_pred_per_seq=args.max_predictions_per_seq,
+        masked_lm_prob=args.masked_token_fraction,
+        vocab_size=vocab_size,
+        seed=args.seed,
+        static_masking=True,
+    )
+    sampler = DistributedSampler(
+        dataset, comm.get_world_size(), rank=comm.get_rank(), seed=args.seed
+    )
+    sampler.set_epoch(0)
+    available = len(sampler) // args.local_batch_size
+    if available < args.eval_batches:
+        raise ValueError(
+            f"--eval_batches {args.eval_batches} x --local_batch_size "
+            f"{args.local_batch_size} needs "
+            f"{args.eval_batches * args.local_batch_size} evaluation samples "
+            f"per rank, but {args.eval_input_dir} supplies {len(sampler)} "
+            f"({available} batches) to each of {comm.get_world_size()} rank(s)"
+        )
+    return make_eval_loader(
+        dataset, sampler, args.local_batch_size, seed=args.seed,
+        num_workers=args.num_workers, pin_memory=torch.cuda.is_available(),
+    )
+
+
+def run_evaluation(args, model, eval_loader, device, autocast_dtype, log, step):
+    # every evaluation starts at the rank's first sample again
+    eval_loader.sampler.index = 0
+    eval_loader.dataset.rewind()
+    metrics = evaluate_pretraining(
+        model, eval_loader, device, autocast_dtype=autocast_dtype,
+        max_predictions_per_seq=args.max_predictions_per_seq,
+        max_batches=args.eval_batches,
+    )
+    if comm.is_main_process():
+        log.log("eval", step + args.previous_phase_end_step, **metrics)
+    return metrics
 
 
 def forward_backward_pass(model, criterion, scaler, batch, args, sync_grads,
@@ -388,6 +453,7 @@ def main(args) -> int:
         args, model, resume_state
     )
     loader, sampler = prepare_dataset(args, resume_state)
+    eval_loader = prepare_eval_loader(args) if args.eval_input_dir else None
 
     autocast_dtype = None
     if args.pure_bf16:
@@ -482,6 +548,19 @@ def main(args) -> int:
                 accum_loss = 0.0
 
                 if (
+                    eval_loader is not None
+                    and args.eval_interval > 0
+                    and global_steps % args.eval_interval == 0
+                ):
+                    eval_start = time.perf_counter()
+                    run_evaluation(args, model, eval_loader, device,
+                                   autocast_dtype, log, global_steps)
+                    # keep evaluation time out of the throughput figures
+                    eval_time = time.perf_counter() - eval_start
+                    window_start += eval_time
+                    train_start += eval_time
+
+                if (
                     args.output_dir
                     and global_steps % args.num_steps_per_checkpoint == 0
                     and comm.is_main_process()
@@ -498,6 +577,9 @@ def main(args) -> int:
                     break
             epoch += 1
 
+    if eval_loader is not None and args.eval_interval <= 0:
+        run_evaluation(args, model, eval_loader, device, autocast_dtype, log,
+                       global_steps)
     if args.output_dir and comm.is_main_process():
         _save_checkpoint(
             args, model, optimizer, sampler, scaler, preconditioner, epoch,
