@@ -12,7 +12,9 @@ Re-designed from the reference's ``ShardedPretrainingDataset``
   schema, plus the legacy NVIDIA pre-masked schema; ``static_masking``
   instead draws the mask of sample ``idx`` from a generator seeded by
   ``(seed, idx)``, so a held-out set is the same tensors at every
-  evaluation, in every run, at any worker count;
+  evaluation, in every run, at any worker count; ``device_masking``
+  masks nothing here and hands out the raw row, its special positions
+  and its global index for ``DeviceMasker`` (masking.py);
 * a rank-chunked sequential sampler whose position checkpoints into the
   training state dict.
 
@@ -51,9 +53,16 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         shuffle: bool = False,
         seed: Optional[int] = None,
         static_masking: bool = False,
+        device_masking: bool = False,
     ):
         if original_token_prob + random_token_prob > 1:
             raise ValueError("original_token_prob + random_token_prob > 1")
+        if device_masking and static_masking:
+            raise ValueError(
+                "device_masking and static_masking are mutually exclusive: "
+                "one masks on the device from (seed, epoch, sample index), "
+                "the other on the CPU from (seed, sample index)"
+            )
         if shuffle:
             raise ValueError(
                 "shuffle is not supported; pre-shuffle samples in the shards"
@@ -71,6 +80,7 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         self.random_token_prob = random_token_prob
         self.seed = seed
         self.static_masking = static_masking
+        self.device_masking = device_masking
         self.epoch = 0
         self._rng = np.random.default_rng(seed)
 
@@ -127,6 +137,9 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         input_ids = self.data["input_ids"][local]
         next_sentence_label = self.data["next_sentence_labels"][local]
 
+        if self.device_masking:
+            return self._raw_item(idx, local, input_ids, next_sentence_label)
+
         if "special_token_positions" in self.data:
             special = self.data["special_token_positions"][local]
             segment_ids = self._segment_ids(input_ids, special)
@@ -160,6 +173,28 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         ]
 
     # -- internals -------------------------------------------------------
+    def _raw_item(self, idx, local, input_ids, next_sentence_label):
+        """device_masking: the unmasked row, its specials as [cls, sep, sep]
+        and its global index; ``DeviceMasker`` does the rest on the device.
+        Draws nothing from ``_rng``."""
+        if "special_token_positions" not in self.data:
+            raise ValueError(
+                f"{self.files[self.file_idx]} is a pre-masked shard (it has "
+                "no special_token_positions): device_masking / "
+                "--device_masking needs unmasked shards; drop the flag to "
+                "train on this one"
+            )
+        special = np.asarray(self.data["special_token_positions"][local])
+        special3 = np.empty(3, dtype=np.int32)
+        special3[: len(special)] = special
+        special3[len(special):] = special[-1]
+        return [
+            np.asarray(input_ids).astype(np.int32),
+            special3,
+            np.asarray(next_sentence_label).astype(np.int64),
+            np.asarray(idx, dtype=np.int64),
+        ]
+
     def _file_for_sample(self, idx: int) -> int:
         for i, (start, end) in enumerate(self.file_idxs):
             if start <= idx < end:

@@ -591,6 +591,11 @@ class BertForPreTraining(BertPreTrainedModel):
     return element is instead the ``ops.MlmEval`` tuple (loss_sum, count,
     correct, pred) of ``ops.mlm_decoder_eval``: no [P, V] scores, no
     autograd graph.
+
+    With ``masked_lm_positions`` (device masking, ``ops.mlm_mask``) the
+    gather is skipped: ``masked_lm_labels`` is then the [P] vector of
+    labels at those flat positions, and everything after the gather is
+    the same code.
     """
 
     def __init__(self, config: BertConfig):
@@ -616,13 +621,19 @@ class BertForPreTraining(BertPreTrainedModel):
         max_predictions_per_seq=None,
         compute_mlm_loss=False,
         mlm_eval=False,
+        masked_lm_positions=None,
     ):
         encoded, pooled = self.bert(input_ids, token_type_ids, attention_mask)
         sequence_output = encoded[-1] if isinstance(encoded, list) else encoded
         if masked_lm_labels is None:
             return self.cls(sequence_output, pooled)
         flat_labels = masked_lm_labels.reshape(-1)
-        if max_predictions_per_seq is not None:
+        if masked_lm_positions is not None:
+            # the gather is already done (ops.mlm_mask): [P] flat positions
+            # and their [P] labels, in the padded layout built below
+            positions = masked_lm_positions
+            gathered_labels = flat_labels
+        elif max_predictions_per_seq is not None:
             # Sync-free padded gather: a fixed [B*max_pred] row budget so no
             # torch.nonzero device->host count sync per micro-batch. Padding
             # slots point at row 0 with label -1, which the CE loss ignores

@@ -177,6 +177,104 @@ def kfac_factor_update(
     factor.copy_(torch.where(coef[1] != 0, new, factor))
 
 
+_LO32 = 0xFFFFFFFF
+
+
+def _mul_hi_lo(m: int, c: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """High and low 32 bits of ``m * c`` (both below 2^32) without leaving
+    the non-negative int64 range: ``c`` is split into 16-bit halves."""
+    a = (c & 0xFFFF) * m  # < 2^48
+    b = (c >> 16) * m  # < 2^48
+    mid = b + (a >> 16)  # product = mid * 2^16 + (a & 0xFFFF)
+    return mid >> 16, ((mid & 0xFFFF) << 16) | (a & 0xFFFF)
+
+
+def philox4x32_10_words(c0, c1, c2, c3, k0: int, k1: int) -> list[torch.Tensor]:
+    """Philox4x32-10 on int64 tensors holding 32-bit counter words and an
+    integer key; the four output words as int64 tensors in [0, 2^32)."""
+    for _ in range(10):
+        hi0, lo0 = _mul_hi_lo(0xD2511F53, c0)
+        hi1, lo1 = _mul_hi_lo(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0 = (k0 + 0x9E3779B9) & _LO32
+        k1 = (k1 + 0xBB67AE85) & _LO32
+    return [c0, c1, c2, c3]
+
+
+def mlm_mask(
+    input_ids: torch.Tensor,
+    special: torch.Tensor,
+    sample_index: torch.Tensor,
+    count_table: torch.Tensor,
+    seed: int,
+    epoch: int,
+    max_pred: int,
+    vocab_size: int,
+    mask_token: int,
+    t_keep: int,
+    t_rand: int,
+) -> tuple[torch.Tensor, ...]:
+    """Dynamic MLM masking of raw shard rows (csrc/ops/mlm_mask.hip in
+    torch integer arithmetic). input_ids [B,S], special [B,3],
+    sample_index [B], count_table [S+1] ->
+    (masked_ids, token_type_ids, attention_mask, positions,
+    gathered_labels, dense_labels), all int64."""
+    bsz, seq = input_ids.shape
+    dev = input_ids.device
+    ids = input_ids.long()
+    sp = special.long()
+    j = torch.arange(seq, device=dev).unsqueeze(0)  # [1, S]
+    s0, s1, s2 = (sp[:, k : k + 1] for k in range(3))  # [B, 1]
+    last = s2.clamp(0, seq - 1)
+    attention_mask = (j <= last).long()
+    token_type = ((j > s1) & (j <= s2)).long()
+    cand = (j < last) & (j != s0) & (j != s1) & (j != s2)
+    n_cand = cand.sum(1)
+    n = torch.minimum(
+        count_table.long()[n_cand].clamp(0, max_pred), n_cand
+    ).unsqueeze(1)
+
+    seed &= 0xFFFFFFFFFFFFFFFF
+    index = sample_index.long().unsqueeze(1)  # two's complement of the u64
+    c2 = (index & _LO32).expand(bsz, seq)
+    c3 = (((index >> 32) & 0x7FFFFFFF) | 0x80000000).expand(bsz, seq)
+    c0 = j.expand(bsz, seq)
+    c1 = torch.full_like(c0, epoch & _LO32)
+    w0, w1, w2, _ = philox4x32_10_words(
+        c0, c1, c2, c3, seed & _LO32, seed >> 32
+    )
+
+    # (w0 << 32 | j) orders like w0 * S + j; non-candidates sort last
+    key = torch.where(cand, w0 * seq + j, torch.full_like(w0, 1 << 62))
+    rank = torch.argsort(torch.argsort(key, dim=1), dim=1)
+    selected = cand & (rank < n)
+
+    random_ids = (w2 * (vocab_size - 1)) >> 32
+    new_ids = torch.where(
+        w1 < t_keep,
+        ids,
+        torch.where(
+            w1 < t_keep + t_rand, random_ids, torch.full_like(ids, mask_token)
+        ),
+    )
+    masked_ids = torch.where(selected, new_ids, ids)
+    labels = torch.where(selected, ids, torch.full_like(ids, -1))
+
+    # the padded gather of BertForPreTraining.forward
+    cap = bsz * max_pred
+    flat = selected.reshape(-1)
+    slots = torch.cumsum(flat.long(), 0) - 1
+    slots = torch.where(flat, slots.clamp(max=cap), torch.full_like(slots, cap))
+    positions = torch.zeros(cap + 1, dtype=torch.long, device=dev)
+    positions.scatter_(0, slots, torch.arange(bsz * seq, device=dev))
+    gathered = torch.full((cap + 1,), -1, dtype=torch.long, device=dev)
+    gathered.scatter_(0, slots, labels.reshape(-1))
+    return (
+        masked_ids, token_type, attention_mask, positions[:cap],
+        gathered[:cap], labels,
+    )
+
+
 def cross_entropy(
     logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -1
 ) -> torch.Tensor:

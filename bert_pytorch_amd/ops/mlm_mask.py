@@ -1,0 +1,122 @@
+"""Dynamic MLM masking as a pure function of (seed, epoch, sample, position).
+
+``mlm_mask`` turns raw shard rows (``input_ids`` and the special-token
+positions) into the model's inputs and the padded-gather MLM positions in
+one HIP launch (csrc/ops/mlm_mask.hip). For each row:
+
+* ``last = clamp(special[2], 0, S-1)``; ``attention_mask[j] = j <= last``;
+  ``token_type[j] = special[1] < j <= special[2]``;
+* candidates are the positions below ``last`` that no special names, and
+  ``n = count_table[#candidates]`` of them are masked;
+* candidate ``j`` draws ``philox4x32_10(counter = (j, epoch, lo32(index),
+  hi32(index) & 0x7FFFFFFF | 0x80000000), key = seed)``; the ``n``
+  smallest ``(w0 << 32) | j`` are selected;
+* a selected token keeps its id when ``w1 < t_keep``, becomes
+  ``(w2 * (vocab_size - 1)) >> 32`` when ``w1 < t_keep + t_rand`` and
+  ``mask_token`` otherwise; its label is the original id.
+
+Nothing depends on the batch a sample sits in, on the worker that read
+it or on the world size, and nothing is read back to the host. No
+autograd: every tensor is an integer.
+"""
+
+from __future__ import annotations
+
+from typing import Optional, Tuple
+
+import torch
+
+from . import _reference, extension, use_native
+
+
+def mlm_thresholds(
+    original_token_prob: float, random_token_prob: float
+) -> Tuple[int, int]:
+    """``(t_keep, t_rand)``: the two probabilities in units of 2^-32,
+    rounded down."""
+    if not (
+        0 <= original_token_prob
+        and 0 <= random_token_prob
+        and original_token_prob + random_token_prob <= 1
+    ):
+        raise ValueError(
+            "original_token_prob and random_token_prob must be >= 0 and sum "
+            f"to at most 1, got {original_token_prob}, {random_token_prob}"
+        )
+    return (
+        int(original_token_prob * (1 << 32)),
+        int(random_token_prob * (1 << 32)),
+    )
+
+
+def mlm_count_table(
+    seq_len: int, masked_lm_prob: float, max_pred: int
+) -> torch.Tensor:
+    """int32 [seq_len + 1]: masked tokens of a row with ``c`` candidates,
+    ``min(max_pred, max(1, int(c * masked_lm_prob)))`` (0 for ``c == 0``),
+    in Python's own arithmetic."""
+    return torch.tensor(
+        [
+            0 if c == 0 else min(max_pred, max(1, int(c * masked_lm_prob)))
+            for c in range(seq_len + 1)
+        ],
+        dtype=torch.int32,
+    )
+
+
+def _signed64(value: int) -> int:
+    value &= 0xFFFFFFFFFFFFFFFF
+    return value - (1 << 64) if value >= 1 << 63 else value
+
+
+def mlm_mask(
+    input_ids: torch.Tensor,
+    special: torch.Tensor,
+    sample_index: torch.Tensor,
+    count_table: torch.Tensor,
+    *,
+    seed: int,
+    epoch: int,
+    max_pred: int,
+    vocab_size: int,
+    mask_token: int,
+    t_keep: int,
+    t_rand: int,
+    dense_labels: bool = False,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+           torch.Tensor, Optional[torch.Tensor]]:
+    """input_ids int32 [B,S], special int32 [B,3] (or [B,2]: the last
+    entry is repeated), sample_index int64 [B], count_table int32 [S+1]
+    (``mlm_count_table``) -> ``(masked_ids, token_type_ids,
+    attention_mask, positions, gathered_labels, labels)``.
+
+    The first three are int64 [B,S]. ``positions`` / ``gathered_labels``
+    are int64 [B*max_pred] in the layout of ``BertForPreTraining``'s
+    padded gather: the masked tokens in ascending flat index, then
+    position 0 with label -1. ``labels`` is the dense int64 [B,S] label
+    tensor (-1 where unmasked) when ``dense_labels`` is set, else None.
+    """
+    if input_ids.dim() != 2:
+        raise ValueError("input_ids must be [B, S]")
+    if special.dim() != 2 or special.shape[1] not in (2, 3):
+        raise ValueError("special must be [B, 2] or [B, 3]")
+    if special.shape[1] == 2:
+        special = torch.cat([special, special[:, 1:]], dim=1)
+    if use_native(input_ids):
+        out = extension().mlm_mask(
+            input_ids, special.contiguous(), sample_index, count_table,
+            _signed64(seed), epoch & 0xFFFFFFFF, max_pred, vocab_size,
+            mask_token, t_keep, t_rand, dense_labels,
+        )
+        return (*out[:5], out[5] if dense_labels else None)
+    seq = input_ids.shape[1]
+    if not (1 <= max_pred <= seq and count_table.numel() == seq + 1):
+        raise ValueError(
+            f"need 1 <= max_pred ({max_pred}) <= S ({seq}) and a count "
+            f"table of S + 1 entries, got {count_table.numel()}"
+        )
+    out = _reference.mlm_mask(
+        input_ids, special, sample_index, count_table, seed, epoch, max_pred,
+        vocab_size, mask_token, t_keep, t_rand,
+    )
+    return (*out[:5], out[5] if dense_labels else None)

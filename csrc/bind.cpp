@@ -57,6 +57,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("factor"), py::arg("coef"),
         py::arg("has_bias"), py::arg("splitk_override") = 0);
   m.def("kfac_factor_supported", &bpa::kfac_factor_supported);
+  m.def("mlm_mask", &bpa::mlm_mask,
+        "dynamic MLM masking + padded-gather positions from raw shard rows",
+        py::arg("input_ids"), py::arg("special"), py::arg("sample_index"),
+        py::arg("count_table"), py::arg("seed"), py::arg("epoch"),
+        py::arg("max_pred"), py::arg("vocab_size"), py::arg("mask_token"),
+        py::arg("t_keep"), py::arg("t_rand"), py::arg("dense_labels") = false);
   m.def("multi_tensor_l2norm_sq", &bpa::multi_tensor_l2norm_sq);
   m.def("multi_tensor_clip_scale", &bpa::multi_tensor_clip_scale);
   m.def("fused_lamb", &bpa::fused_lamb);

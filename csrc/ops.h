@@ -129,6 +129,19 @@ torch::Tensor attention_varlen_bwd(torch::Tensor dout, torch::Tensor qkv,
 torch::Tensor pack_rows(torch::Tensor x, torch::Tensor dest, int64_t t_pad);
 torch::Tensor unpack_rows(torch::Tensor y, torch::Tensor dest,
                           int64_t padded_rows);
+// mlm_mask.hip: dynamic MLM masking of raw shard rows. input_ids i32 [B,S],
+// special i32 [B,3], sample_index i64 [B], count_table i32 [S+1] ->
+// {masked_ids, token_type_ids, attention_mask} i64 [B,S], {positions,
+// gathered_labels} i64 [B*max_pred] (+ dense labels i64 [B,S] on request).
+// seed carries the bits of a uint64; t_keep, t_rand are in units of 2^-32.
+std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
+                                    torch::Tensor special,
+                                    torch::Tensor sample_index,
+                                    torch::Tensor count_table, int64_t seed,
+                                    int64_t epoch, int64_t max_pred,
+                                    int64_t vocab_size, int64_t mask_token,
+                                    int64_t t_keep, int64_t t_rand,
+                                    bool dense_labels);
 torch::Tensor multi_tensor_l2norm_sq(std::vector<torch::Tensor> tensors);
 void multi_tensor_clip_scale(std::vector<torch::Tensor> grads,
                              torch::Tensor gnorm_sq, double max_norm);

@@ -29,7 +29,11 @@ import numpy as np
 import torch
 
 from bert_pytorch_amd.config import BertConfig, merge_config_and_args
-from bert_pytorch_amd.data import DistributedSampler, ShardedPretrainingDataset
+from bert_pytorch_amd.data import (
+    DeviceMasker,
+    DistributedSampler,
+    ShardedPretrainingDataset,
+)
 from bert_pytorch_amd.evaluation import evaluate_pretraining, make_eval_loader
 from bert_pytorch_amd.models import BertForPreTraining, BertPretrainingCriterion
 from bert_pytorch_amd.optim import FusedLAMB, PolyWarmUpScheduler
@@ -91,6 +95,13 @@ def parse_arguments(args=None) -> argparse.Namespace:
                         help="run the encoder on the valid tokens only "
                              "(packed rows + variable-length attention); "
                              "off by default, not available with --kfac")
+    parser.add_argument("--device_masking", action="store_true",
+                        help="mask training batches on the device "
+                             "(ops.mlm_mask): the loader ships raw rows and "
+                             "a sample's mask depends on (--seed, epoch, "
+                             "sample index) only, not on --num_workers, the "
+                             "world size or a resume; needs unmasked shards; "
+                             "evaluation keeps its static CPU masks")
     parser.add_argument("--vocab_file", type=str, default=None)
     parser.add_argument("--mask_token_index", type=int, default=None)
     parser.add_argument("--vocab_pad_multiple", type=int, default=64,
@@ -125,7 +136,7 @@ def parse_arguments(args=None) -> argparse.Namespace:
     ns = merge_config_and_args(parser, args)
     # bool-ish JSON values
     for key in ("fp16", "bf16", "bf16_weights", "kfac", "disable_progress_bar",
-                "checkpoint_activations", "unpad"):
+                "checkpoint_activations", "unpad", "device_masking"):
         setattr(ns, key, bool(getattr(ns, key)))
     if ns.unpad and ns.kfac:
         raise ValueError(
@@ -334,6 +345,7 @@ def prepare_dataset(args, resume_state):
         masked_lm_prob=args.masked_token_fraction,
         vocab_size=vocab_size,
         seed=args.seed,
+        device_masking=args.device_masking,
     )
     sampler = DistributedSampler(
         dataset, comm.get_world_size(), rank=comm.get_rank(), seed=args.seed
@@ -351,6 +363,20 @@ def prepare_dataset(args, resume_state):
         persistent_workers=args.num_workers > 0,
     )
     return loader, sampler
+
+
+def prepare_masker(args):
+    """--device_masking: the on-device masker of the training batches. Its
+    seed is --seed itself, not --seed + rank: a sample's mask is the same
+    at any world size."""
+    mask_index, vocab_size = _mask_index_and_vocab(args)
+    return DeviceMasker(
+        seed=args.seed,
+        mask_token_index=mask_index,
+        max_pred_per_seq=args.max_predictions_per_seq,
+        masked_lm_prob=args.masked_token_fraction,
+        vocab_size=vocab_size,
+    )
 
 
 def prepare_eval_loader(args):
@@ -405,7 +431,12 @@ def run_evaluation(args, model, eval_loader, device, autocast_dtype, log, step):
 
 def forward_backward_pass(model, criterion, scaler, batch, args, sync_grads,
                           autocast_dtype, timer):
-    input_ids, segment_ids, input_mask, mlm_labels, nsp_labels = batch
+    if len(batch) == 6:  # --device_masking: the gather is already done
+        (input_ids, segment_ids, input_mask, mlm_positions, mlm_labels,
+         nsp_labels) = batch
+    else:
+        input_ids, segment_ids, input_mask, mlm_labels, nsp_labels = batch
+        mlm_positions = None
     enabled = autocast_dtype is not None
     with timer.phase("forward"), torch.autocast(
         device_type="cuda" if input_ids.is_cuda else "cpu",
@@ -415,7 +446,7 @@ def forward_backward_pass(model, criterion, scaler, batch, args, sync_grads,
         scores, seq_rel, gathered_labels = model(
             input_ids, segment_ids, input_mask, masked_lm_labels=mlm_labels,
             max_predictions_per_seq=args.max_predictions_per_seq,
-            compute_mlm_loss=True,
+            compute_mlm_loss=True, masked_lm_positions=mlm_positions,
         )
         loss = criterion(scores, seq_rel, gathered_labels, nsp_labels)
         loss = loss / args.accumulation_steps
@@ -453,6 +484,7 @@ def main(args) -> int:
         args, model, resume_state
     )
     loader, sampler = prepare_dataset(args, resume_state)
+    masker = prepare_masker(args) if args.device_masking else None
     eval_loader = prepare_eval_loader(args) if args.eval_input_dir else None
 
     autocast_dtype = None
@@ -509,6 +541,8 @@ def main(args) -> int:
                 micro_step += 1
                 with timer.phase("h2d"):
                     batch = [t.to(device, non_blocking=True) for t in batch]
+                    if masker is not None:
+                        batch = masker(batch, epoch)
                 sync_grads = micro_step % args.accumulation_steps == 0
                 loss = forward_backward_pass(
                     model, criterion, scaler, batch, args, sync_grads,

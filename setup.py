@@ -26,6 +26,7 @@ sources = [
     "csrc/ops/wgrad.hip",
     "csrc/ops/kfac_factor.hip",
     "csrc/ops/mlm_head.hip",
+    "csrc/ops/mlm_mask.hip",
     "csrc/ops/mfma_probe.hip",
     "csrc/ops/gemm_epilogue.cpp",
     "csrc/optim/multi_tensor.hip",
