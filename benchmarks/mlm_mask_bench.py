@@ -13,7 +13,12 @@ Default mode alternates the two in one process: each round times every
 contender once (device events around ITERS back-to-back calls) and the
 table reports the median over rounds with the min-max spread.
 
-``--trace mask|gather`` instead issues ``--calls`` calls of one contender
+``--whole_word`` times whole-word masking instead of the gather:
+  wwm     ops.mlm_mask(..., word_continues=table): the selection kernel
+          and the scatter kernel, two launches, on the same rows, with a
+          table that marks a fifth of the vocabulary as continuation pieces
+
+``--trace mask|gather|wwm`` instead issues ``--calls`` calls of one contender
 per shape after a warm-up and nothing else, for a kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- \
         python benchmarks/mlm_mask_bench.py --trace mask
@@ -41,6 +46,7 @@ DEV = "cuda:0"
 ROUNDS, ITERS, WARMUP = 15, 50, 10
 VOCAB, MASK_TOKEN, PROB = 30522, 103, 0.15
 SHAPES = [(96, 128, 20), (16, 512, 76)]
+CONTINUES = 0.2  # --whole_word: share of the vocabulary that continues a word
 
 
 def make_rows(bsz, seq, seed):
@@ -78,17 +84,38 @@ def padded_gather(masked_lm_labels, max_predictions_per_seq):
     return positions[:cap], gathered_labels[:cap]
 
 
-def contenders(bsz, seq, max_pred):
+def contenders(bsz, seq, max_pred, whole_word=False):
     ids, special, index = make_rows(bsz, seq, seed=bsz + seq)
     table = ops.mlm_count_table(seq, PROB, max_pred).to(DEV)
     t_keep, t_rand = ops.mlm_thresholds(0.1, 0.1)
 
-    def run_mask(dense=False):
+    def run_mask(dense=False, word_continues=None):
         return ops.mlm_mask(
             ids, special, index, table, seed=42, epoch=0, max_pred=max_pred,
             vocab_size=VOCAB, mask_token=MASK_TOKEN, t_keep=t_keep,
-            t_rand=t_rand, dense_labels=dense,
+            t_rand=t_rand, dense_labels=dense, word_continues=word_continues,
         )
+
+    if whole_word:
+        # a fifth of the (uniformly drawn) ids continue a word: words of
+        # 1.25 pieces on average, as WordPiece gives on English text
+        rng = np.random.default_rng(bsz * seq)
+        words = torch.from_numpy(
+            (rng.random(VOCAB) < CONTINUES).astype(np.uint8)
+        ).to(DEV)
+        zeros = torch.zeros_like(words)
+
+        def run_wwm():
+            return run_mask(word_continues=words)
+
+        # with no continuation pieces the two paths are one function
+        plain = run_mask(dense=True)
+        for a, b in zip(plain, run_mask(dense=True, word_continues=zeros)):
+            assert torch.equal(a, b)
+        got = run_mask(dense=True, word_continues=words)
+        positions, gathered = padded_gather(got[5], max_pred)
+        assert torch.equal(positions, got[3]) and torch.equal(gathered, got[4])
+        return {"mask": run_mask, "wwm": run_wwm}
 
     out = run_mask(dense=True)
     labels = out[5]
@@ -115,7 +142,7 @@ def time_once(fn):
 
 def trace(which, calls):
     for bsz, seq, max_pred in SHAPES:
-        fn = contenders(bsz, seq, max_pred)[which]
+        fn = contenders(bsz, seq, max_pred, whole_word=which == "wwm")[which]
         for _ in range(WARMUP):
             fn()
         torch.cuda.synchronize()
@@ -129,24 +156,32 @@ def trace(which, calls):
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--out", default=None, help="also write the table here")
-    parser.add_argument("--trace", choices=["mask", "gather"], default=None)
+    parser.add_argument("--trace", choices=["mask", "gather", "wwm"],
+                        default=None)
     parser.add_argument("--calls", type=int, default=200)
+    parser.add_argument("--whole_word", action="store_true",
+                        help="time whole-word masking (word_continues=, two "
+                             "launches) against token-level ops.mlm_mask")
     args = parser.parse_args()
     assert torch.cuda.is_available(), "this benchmark needs a GPU"
     if args.trace:
         trace(args.trace, args.calls)
         return
 
+    second = (
+        "ops.mlm_mask, whole words" if args.whole_word
+        else "padded gather (torch)"
+    )
     lines = [
         f"device: {torch.cuda.get_device_name(0)}; {ROUNDS} alternating rounds "
         f"x {ITERS} back-to-back calls, median us per call (min-max over "
         "rounds), host launch cost included",
         "",
-        "| B | S | max_pred | ops.mlm_mask | padded gather (torch) |",
+        f"| B | S | max_pred | ops.mlm_mask | {second} |",
         "|---|---|---|---|---|",
     ]
     for bsz, seq, max_pred in SHAPES:
-        fns = list(contenders(bsz, seq, max_pred).values())
+        fns = list(contenders(bsz, seq, max_pred, args.whole_word).values())
         for fn in fns:
             for _ in range(WARMUP):
                 fn()

@@ -15,6 +15,9 @@ Re-designed from the reference's ``ShardedPretrainingDataset``
   evaluation, in every run, at any worker count; ``device_masking``
   masks nothing here and hands out the raw row, its special positions
   and its global index for ``DeviceMasker`` (masking.py);
+  ``whole_word_masking`` makes the dynamic masks of whole words (the word
+  rule and greedy fill of ``ops.mlm_mask``, drawn from this dataset's
+  generator); static masks stay token-level;
 * a rank-chunked sequential sampler whose position checkpoints into the
   training state dict.
 
@@ -54,9 +57,24 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         seed: Optional[int] = None,
         static_masking: bool = False,
         device_masking: bool = False,
+        whole_word_masking: bool = False,
+        word_continues=None,
     ):
         if original_token_prob + random_token_prob > 1:
             raise ValueError("original_token_prob + random_token_prob > 1")
+        if whole_word_masking and not (device_masking or static_masking):
+            if word_continues is None:
+                raise ValueError(
+                    "whole_word_masking needs word_continues, the uint8 "
+                    "[vocab_size] table of tokenization."
+                    "word_continuation_table"
+                )
+            word_continues = np.asarray(word_continues, dtype=np.uint8)
+            if word_continues.shape != (vocab_size,):
+                raise ValueError(
+                    f"word_continues must be uint8 [{vocab_size}], got shape "
+                    f"{word_continues.shape}"
+                )
         if device_masking and static_masking:
             raise ValueError(
                 "device_masking and static_masking are mutually exclusive: "
@@ -81,6 +99,12 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         self.seed = seed
         self.static_masking = static_masking
         self.device_masking = device_masking
+        # static (evaluation) masks stay token-level and device_masking
+        # masks nothing here: whole words are a matter of the dynamic path
+        self.whole_word_masking = (
+            whole_word_masking and not (device_masking or static_masking)
+        )
+        self.word_continues = word_continues if self.whole_word_masking else None
         self.epoch = 0
         self._rng = np.random.default_rng(seed)
 
@@ -155,6 +179,13 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
                 input_ids, special, rng
             )
         else:  # legacy NVIDIA pre-masked format
+            if self.whole_word_masking:
+                raise ValueError(
+                    f"{self.files[self.file_idx]} is a pre-masked shard (it "
+                    "has no special_token_positions): whole_word_masking / "
+                    "--whole_word_masking needs unmasked shards; drop the "
+                    "flag to train on this one"
+                )
             segment_ids = self.data["segment_ids"][local]
             input_mask = self.data["input_mask"][local]
             masked_input_ids = input_ids
@@ -245,7 +276,13 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
             self.max_pred_per_seq,
             max(1, int(candidates.size * self.masked_lm_prob)),
         )
-        mask_indices = rng.choice(candidates, mask_count, replace=False)
+        if self.whole_word_masking:
+            mask_indices = self._whole_word_indices(
+                input_ids, candidates, mask_count, rng
+            )
+            mask_count = mask_indices.size
+        else:
+            mask_indices = rng.choice(candidates, mask_count, replace=False)
         masked_lm_labels[mask_indices] = input_ids[mask_indices]
         draws = rng.random(mask_count)
         for idx, draw in zip(mask_indices, draws):
@@ -256,6 +293,38 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
             else:
                 input_ids[idx] = self.mask_token_index
         return input_ids, masked_lm_labels
+
+    def _whole_word_indices(
+        self,
+        input_ids: np.ndarray,
+        candidates: np.ndarray,
+        mask_count: int,
+        rng: np.random.Generator,
+    ) -> np.ndarray:
+        """Whole-word selection, the rule of ``ops.mlm_mask`` with this
+        dataset's generator: a candidate starts a word unless its id
+        continues one and the position before it is a candidate; the words
+        are visited in a random order and one is taken, all of it, when it
+        still fits into ``mask_count``, until ``mask_count`` is reached."""
+        words: List[List[int]] = []
+        for j in candidates.tolist():
+            token = int(input_ids[j])
+            continues = (
+                0 <= token < self.word_continues.size
+                and self.word_continues[token] == 1
+            )
+            if continues and words and words[-1][-1] == j - 1:
+                words[-1].append(j)
+            else:
+                words.append([j])
+        chosen: List[int] = []
+        for w in rng.permutation(len(words)):
+            if len(chosen) >= mask_count:
+                break
+            if len(chosen) + len(words[w]) > mask_count:
+                continue
+            chosen.extend(words[w])
+        return np.array(chosen, dtype=np.int64)
 
     @staticmethod
     def _premasked_labels(

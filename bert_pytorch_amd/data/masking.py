@@ -10,7 +10,7 @@ lands in, or whether the run was resumed.
 
 from __future__ import annotations
 
-from typing import Dict, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -27,7 +27,11 @@ class DeviceMasker:
         vocab_size: int,
         original_token_prob: float = 0.1,
         random_token_prob: float = 0.1,
+        word_continues: Optional[torch.Tensor] = None,
     ):
+        """``word_continues`` (uint8 [vocab_size],
+        ``tokenization.word_continuation_table``) turns on whole-word
+        masking."""
         self.seed = int(seed)
         self.mask_token_index = int(mask_token_index)
         self.max_pred_per_seq = int(max_pred_per_seq)
@@ -37,6 +41,27 @@ class DeviceMasker:
             original_token_prob, random_token_prob
         )
         self._tables: Dict[Tuple[int, torch.device], torch.Tensor] = {}
+        if word_continues is not None:
+            word_continues = torch.as_tensor(word_continues)
+            if (
+                word_continues.dtype != torch.uint8
+                or word_continues.shape != (self.vocab_size,)
+            ):
+                raise ValueError(
+                    f"word_continues must be uint8 [{self.vocab_size}], got "
+                    f"{word_continues.dtype} {tuple(word_continues.shape)}"
+                )
+        self.word_continues = word_continues
+        self._word_tables: Dict[torch.device, torch.Tensor] = {}
+
+    def word_table(self, device: torch.device) -> Optional[torch.Tensor]:
+        """``word_continues`` on ``device``, uploaded once; None when
+        masking is token-level."""
+        if self.word_continues is None:
+            return None
+        if device not in self._word_tables:
+            self._word_tables[device] = self.word_continues.to(device)
+        return self._word_tables[device]
 
     def count_table(self, seq_len: int, device: torch.device) -> torch.Tensor:
         """``ops.mlm_count_table`` for this sequence length, uploaded once."""
@@ -58,5 +83,6 @@ class DeviceMasker:
             seed=self.seed, epoch=epoch, max_pred=self.max_pred_per_seq,
             vocab_size=self.vocab_size, mask_token=self.mask_token_index,
             t_keep=self.t_keep, t_rand=self.t_rand,
+            word_continues=self.word_table(input_ids.device),
         )
         return masked, segment_ids, input_mask, positions, gathered, nsp_labels

@@ -16,6 +16,8 @@ fallback keeps CPU-only environments working.
 
 from __future__ import annotations
 
+import json
+import re
 import unicodedata
 from typing import Dict, List, Optional, Sequence
 
@@ -262,21 +264,57 @@ _BYTE_ENC = _bytes_to_unicode()
 _BYTE_DEC = {v: k for k, v in _BYTE_ENC.items()}
 
 
+def load_bpe_vocab(vocab_file: str) -> Dict[str, int]:
+    """A ``vocab.json`` (token -> id), or one token per line."""
+    with open(vocab_file, "r", encoding="utf-8") as f:
+        if f.read(1) == "{":
+            f.seek(0)
+            return json.load(f)
+    return load_vocab(vocab_file)
+
+
+_SPECIAL_TOKEN = re.compile(r"\[[^\[\]\s]+\]|<[^<>\s]+>")
+
+
+def word_continuation_table(vocab_file: str, vocab_size: int):
+    """uint8 tensor [vocab_size] for whole-word masking: 1 where a
+    vocabulary entry continues the word of the piece before it.
+
+    A byte-level BPE vocabulary (one with ``Ġ`` entries; ``vocab.json`` or
+    one token per line) marks a word's first piece with ``Ġ``: every other
+    entry continues. A WordPiece vocabulary marks the continuing pieces
+    with ``##``. Special tokens (``[CLS]``, ``<s>``, ``[unused7]``, ...)
+    and the entries from the end of the vocabulary up to ``vocab_size``
+    (the ``vocab_pad_multiple`` padding) are 0.
+    """
+    import torch  # noqa: PLC0415
+
+    vocab = load_bpe_vocab(vocab_file)
+    if not vocab or max(vocab.values()) >= vocab_size:
+        raise ValueError(
+            f"{vocab_file} has ids up to "
+            f"{max(vocab.values()) if vocab else None}: it needs a "
+            f"vocab_size above that, got {vocab_size}"
+        )
+    byte_level = any(token.startswith("Ġ") for token in vocab)
+    table = torch.zeros(vocab_size, dtype=torch.uint8)
+    for token, index in vocab.items():
+        if _SPECIAL_TOKEN.fullmatch(token):
+            continue
+        if byte_level:
+            continues = not token.startswith("Ġ")
+        else:
+            continues = token.startswith("##")
+        table[index] = int(continues)
+    return table
+
+
 class ByteLevelBPETokenizer:
     """Byte-level BPE over the C++ merge core (RoBERTa-style)."""
 
     def __init__(self, vocab_file: str, merges_file: str,
                  lowercase: bool = False):
-        import json  # noqa: PLC0415
-
-        with open(vocab_file, "r", encoding="utf-8") as f:
-            first = f.read(1)
-            f.seek(0)
-            if first == "{":
-                self.vocab = json.load(f)
-            else:
-                self.vocab = {line.rstrip("\n"): i for i, line in enumerate(f)
-                              if line.rstrip("\n")}
+        self.vocab = load_bpe_vocab(vocab_file)
         self.ids_to_tokens = {i: t for t, i in self.vocab.items()}
         with open(merges_file, "r", encoding="utf-8") as f:
             merges = [ln.rstrip("\n") for ln in f

@@ -201,24 +201,11 @@ def philox4x32_10_words(c0, c1, c2, c3, k0: int, k1: int) -> list[torch.Tensor]:
     return [c0, c1, c2, c3]
 
 
-def mlm_mask(
-    input_ids: torch.Tensor,
-    special: torch.Tensor,
-    sample_index: torch.Tensor,
-    count_table: torch.Tensor,
-    seed: int,
-    epoch: int,
-    max_pred: int,
-    vocab_size: int,
-    mask_token: int,
-    t_keep: int,
-    t_rand: int,
-) -> tuple[torch.Tensor, ...]:
-    """Dynamic MLM masking of raw shard rows (csrc/ops/mlm_mask.hip in
-    torch integer arithmetic). input_ids [B,S], special [B,3],
-    sample_index [B], count_table [S+1] ->
-    (masked_ids, token_type_ids, attention_mask, positions,
-    gathered_labels, dense_labels), all int64."""
+def _mlm_mask_draws(
+    input_ids, special, sample_index, count_table, seed, epoch, max_pred
+):
+    """What both mask functions share up to the selection: ``(ids,
+    token_type, attention_mask, cand, n, j, w0, w1, w2)``."""
     bsz, seq = input_ids.shape
     dev = input_ids.device
     ids = input_ids.long()
@@ -243,12 +230,16 @@ def mlm_mask(
     w0, w1, w2, _ = philox4x32_10_words(
         c0, c1, c2, c3, seed & _LO32, seed >> 32
     )
+    return ids, token_type, attention_mask, cand, n, j, w0, w1, w2
 
-    # (w0 << 32 | j) orders like w0 * S + j; non-candidates sort last
-    key = torch.where(cand, w0 * seq + j, torch.full_like(w0, 1 << 62))
-    rank = torch.argsort(torch.argsort(key, dim=1), dim=1)
-    selected = cand & (rank < n)
 
+def _mlm_mask_outputs(
+    ids, token_type, attention_mask, selected, w1, w2, max_pred, vocab_size,
+    mask_token, t_keep, t_rand,
+):
+    """Token substitution at the selected positions and the padded gather."""
+    bsz, seq = ids.shape
+    dev = ids.device
     random_ids = (w2 * (vocab_size - 1)) >> 32
     new_ids = torch.where(
         w1 < t_keep,
@@ -272,6 +263,94 @@ def mlm_mask(
     return (
         masked_ids, token_type, attention_mask, positions[:cap],
         gathered[:cap], labels,
+    )
+
+
+def mlm_mask(
+    input_ids: torch.Tensor,
+    special: torch.Tensor,
+    sample_index: torch.Tensor,
+    count_table: torch.Tensor,
+    seed: int,
+    epoch: int,
+    max_pred: int,
+    vocab_size: int,
+    mask_token: int,
+    t_keep: int,
+    t_rand: int,
+) -> tuple[torch.Tensor, ...]:
+    """Dynamic MLM masking of raw shard rows (csrc/ops/mlm_mask.hip in
+    torch integer arithmetic). input_ids [B,S], special [B,3],
+    sample_index [B], count_table [S+1] ->
+    (masked_ids, token_type_ids, attention_mask, positions,
+    gathered_labels, dense_labels), all int64."""
+    ids, token_type, attention_mask, cand, n, j, w0, w1, w2 = _mlm_mask_draws(
+        input_ids, special, sample_index, count_table, seed, epoch, max_pred
+    )
+    seq = ids.shape[1]
+    # (w0 << 32 | j) orders like w0 * S + j; non-candidates sort last
+    key = torch.where(cand, w0 * seq + j, torch.full_like(w0, 1 << 62))
+    rank = torch.argsort(torch.argsort(key, dim=1), dim=1)
+    selected = cand & (rank < n)
+    return _mlm_mask_outputs(
+        ids, token_type, attention_mask, selected, w1, w2, max_pred,
+        vocab_size, mask_token, t_keep, t_rand,
+    )
+
+
+def mlm_mask_whole_word(
+    input_ids: torch.Tensor,
+    special: torch.Tensor,
+    sample_index: torch.Tensor,
+    count_table: torch.Tensor,
+    word_continues: torch.Tensor,
+    seed: int,
+    epoch: int,
+    max_pred: int,
+    vocab_size: int,
+    mask_token: int,
+    t_keep: int,
+    t_rand: int,
+) -> tuple[torch.Tensor, ...]:
+    """``mlm_mask`` with whole-word masking (the two whole-word kernels of
+    csrc/ops/mlm_mask.hip in torch integer arithmetic). word_continues
+    uint8 [vocab_size] is 1 where a vocabulary entry continues a word."""
+    ids, token_type, attention_mask, cand, n, j, w0, w1, w2 = _mlm_mask_draws(
+        input_ids, special, sample_index, count_table, seed, epoch, max_pred
+    )
+    bsz, seq = ids.shape
+    n = n.squeeze(1)
+
+    # words: a candidate starts one unless its id continues a candidate
+    in_vocab = (ids >= 0) & (ids < vocab_size)
+    continues = word_continues.long()[ids.clamp(0, vocab_size - 1)] == 1
+    prev_cand = torch.cat(
+        [torch.zeros_like(cand[:, :1]), cand[:, :-1]], dim=1
+    )
+    start = cand & ~(in_vocab & continues & prev_cand)
+    head = torch.cummax(
+        torch.where(start, j, torch.full_like(j, -1)), dim=1
+    ).values.clamp(min=0)  # of a candidate: the start of its word
+    length = torch.zeros_like(ids).scatter_add_(1, head, cand.long())
+
+    # ascending (w0 << 32 | first), then the greedy fill, a rank at a time
+    key = torch.where(start, w0 * seq + j, torch.full_like(w0, 1 << 62))
+    order = torch.argsort(key, dim=1)
+    length_by_rank = length.gather(1, order)
+    start_by_rank = start.gather(1, order)
+    taken = torch.zeros_like(start)
+    m = torch.zeros_like(n)
+    for r in range(int(start.sum(1).max()) if bsz else 0):
+        fits = start_by_rank[:, r] & (m < n) & (m + length_by_rank[:, r] <= n)
+        m = m + torch.where(fits, length_by_rank[:, r], torch.zeros_like(m))
+        taken[:, r] = fits
+        if bool((m >= n).all()):
+            break
+    word_selected = torch.zeros_like(start).scatter_(1, order, taken)
+    selected = cand & word_selected.gather(1, head)
+    return _mlm_mask_outputs(
+        ids, token_type, attention_mask, selected, w1, w2, max_pred,
+        vocab_size, mask_token, t_keep, t_rand,
     )
 
 

@@ -15,6 +15,13 @@ one HIP launch (csrc/ops/mlm_mask.hip). For each row:
   ``(w2 * (vocab_size - 1)) >> 32`` when ``w1 < t_keep + t_rand`` and
   ``mask_token`` otherwise; its label is the original id.
 
+With a ``word_continues`` table the selection is by whole words (two
+launches): candidate ``j`` starts a word unless ``word_continues[id[j]]``
+is 1 and ``j - 1`` is a candidate; the words are visited in ascending
+``(w0 << 32) | first`` of their first position and one is selected, all
+of it, when it still fits into ``n``, until ``n`` is reached
+(docs/KERNELS.md has the full definition).
+
 Nothing depends on the batch a sample sits in, on the worker that read
 it or on the world size, and nothing is read back to the host. No
 autograd: every tensor is an integer.
@@ -69,6 +76,41 @@ def _signed64(value: int) -> int:
     return value - (1 << 64) if value >= 1 << 63 else value
 
 
+def _mlm_mask_whole_word(
+    input_ids, special, sample_index, count_table, word_continues, seed,
+    epoch, max_pred, vocab_size, mask_token, t_keep, t_rand, dense_labels,
+):
+    if use_native(input_ids):
+        out = extension().mlm_mask_whole_word(
+            input_ids, special.contiguous(), sample_index, count_table,
+            word_continues, _signed64(seed), epoch & 0xFFFFFFFF, max_pred,
+            vocab_size, mask_token, t_keep, t_rand, dense_labels,
+        )
+        return (*out[:5], out[5] if dense_labels else None)
+    seq = input_ids.shape[1]
+    if not (1 <= max_pred <= seq and count_table.numel() == seq + 1):
+        raise ValueError(
+            f"need 1 <= max_pred ({max_pred}) <= S ({seq}) and a count "
+            f"table of S + 1 entries, got {count_table.numel()}"
+        )
+    if (
+        word_continues.device != input_ids.device
+        or word_continues.dtype != torch.uint8
+        or word_continues.dim() != 1
+        or word_continues.numel() != vocab_size
+    ):
+        raise ValueError(
+            f"word_continues must be uint8 [{vocab_size}] on the device of "
+            f"input_ids, got {word_continues.dtype} "
+            f"{tuple(word_continues.shape)} on {word_continues.device}"
+        )
+    out = _reference.mlm_mask_whole_word(
+        input_ids, special, sample_index, count_table, word_continues, seed,
+        epoch, max_pred, vocab_size, mask_token, t_keep, t_rand,
+    )
+    return (*out[:5], out[5] if dense_labels else None)
+
+
 def mlm_mask(
     input_ids: torch.Tensor,
     special: torch.Tensor,
@@ -83,6 +125,7 @@ def mlm_mask(
     t_keep: int,
     t_rand: int,
     dense_labels: bool = False,
+    word_continues: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
            torch.Tensor, Optional[torch.Tensor]]:
     """input_ids int32 [B,S], special int32 [B,3] (or [B,2]: the last
@@ -95,6 +138,10 @@ def mlm_mask(
     padded gather: the masked tokens in ascending flat index, then
     position 0 with label -1. ``labels`` is the dense int64 [B,S] label
     tensor (-1 where unmasked) when ``dense_labels`` is set, else None.
+
+    ``word_continues`` (uint8 [vocab_size], 1 where a vocabulary entry
+    continues a word; ``data.tokenization.word_continuation_table``)
+    switches to whole-word masking, see above.
     """
     if input_ids.dim() != 2:
         raise ValueError("input_ids must be [B, S]")
@@ -102,6 +149,12 @@ def mlm_mask(
         raise ValueError("special must be [B, 2] or [B, 3]")
     if special.shape[1] == 2:
         special = torch.cat([special, special[:, 1:]], dim=1)
+    if word_continues is not None:
+        return _mlm_mask_whole_word(
+            input_ids, special, sample_index, count_table, word_continues,
+            seed, epoch, max_pred, vocab_size, mask_token, t_keep, t_rand,
+            dense_labels,
+        )
     if use_native(input_ids):
         out = extension().mlm_mask(
             input_ids, special.contiguous(), sample_index, count_table,

@@ -142,6 +142,13 @@ std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
                                     int64_t vocab_size, int64_t mask_token,
                                     int64_t t_keep, int64_t t_rand,
                                     bool dense_labels);
+// The same with whole-word masking: word_continues u8 [vocab_size] is 1 where
+// a vocabulary entry continues a word; words are masked whole or not at all.
+std::vector<torch::Tensor> mlm_mask_whole_word(
+    torch::Tensor input_ids, torch::Tensor special, torch::Tensor sample_index,
+    torch::Tensor count_table, torch::Tensor word_continues, int64_t seed,
+    int64_t epoch, int64_t max_pred, int64_t vocab_size, int64_t mask_token,
+    int64_t t_keep, int64_t t_rand, bool dense_labels);
 torch::Tensor multi_tensor_l2norm_sq(std::vector<torch::Tensor> tensors);
 void multi_tensor_clip_scale(std::vector<torch::Tensor> grads,
                              torch::Tensor gnorm_sq, double max_norm);

@@ -15,6 +15,16 @@
 // row), so there is no communication between workgroups and no atomic. The
 // last block also fills the unused tail of the slot budget. Nothing is read
 // back to the host.
+//
+// Whole-word masking (mlm_mask_whole_word) groups the candidates into words
+// with a uint8 [vocab_size] table of continuation pieces, orders the words
+// by the key of their first position and fills the budget greedily, whole
+// words only. A row's count is then no function of its specials, so the
+// work is two launches on one stream: the selection kernel (one workgroup
+// per row) writes the [B,S] outputs, the row's count and its compact list
+// of positions and labels; the scatter kernel sums the counts of the rows
+// before its own and moves the lists to their slots. Still no atomic, no
+// waiting between workgroups and no read-back.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -154,16 +164,260 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// whole-word masking
+// ---------------------------------------------------------------------------
+// Position j of a row belongs to thread j % 256 in every phase, so what a
+// position draws stays in that thread's registers, and a wave's ballot is
+// the 64-bit word j / 64 of a row-wide bit mask in LDS.
+constexpr int kMaskPerThread = kMaskMaxS / kMaskThreads;  // 4
+constexpr int kMaskWords = kMaskMaxS / WAVE_SIZE;         // 16
+
+// first set bit above position j, kMaskMaxS if there is none
+__device__ __forceinline__ int next_set_after(const uint64_t* bits, int j) {
+  int w = j >> 6;
+  uint64_t m = bits[w] & ~((uint64_t{2} << (j & 63)) - 1);
+  while (m == 0 && ++w < kMaskWords) m = bits[w];
+  return m != 0 ? (w << 6) + __builtin_ctzll(m) : kMaskMaxS;
+}
+
+// last set bit at or below position j, -1 if there is none
+__device__ __forceinline__ int last_set_upto(const uint64_t* bits, int j) {
+  int w = j >> 6;
+  uint64_t m = bits[w] & ((uint64_t{2} << (j & 63)) - 1);
+  while (m == 0 && --w >= 0) m = bits[w];
+  return m != 0 ? (w << 6) + 63 - __builtin_clzll(m) : -1;
+}
+
+__global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_select_kernel(
+    const int32_t* __restrict__ ids, const int32_t* __restrict__ special,
+    const int64_t* __restrict__ sample_index,
+    const int32_t* __restrict__ table,
+    const uint8_t* __restrict__ word_continues, int64_t* __restrict__ out_ids,
+    int64_t* __restrict__ out_tt, int64_t* __restrict__ out_am,
+    int64_t* __restrict__ dense,  // may be null
+    int32_t* __restrict__ row_count, int32_t* __restrict__ row_pos,
+    int32_t* __restrict__ row_label, int S, int max_pred, uint64_t seed,
+    uint32_t epoch, uint32_t vocab_size, int64_t mask_token, uint64_t t_keep,
+    uint64_t t_keep_rand) {
+  __shared__ uint64_t keys[kMaskMaxS];
+  __shared__ uint32_t order[kMaskMaxS];  // first | len << 16, by rank
+  __shared__ uint8_t word_sel[kMaskMaxS];
+  __shared__ uint64_t cand_bits[kMaskWords];
+  __shared__ uint64_t start_bits[kMaskWords];
+  __shared__ uint64_t break_bits[kMaskWords];
+  __shared__ uint64_t sel_bits[kMaskWords];
+
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE_SIZE - 1);
+
+  const int32_t* sp = special + 3 * b;
+  const int s0 = sp[0], s1 = sp[1], s2 = sp[2];
+  const int last = min(max(s2, 0), S - 1);
+  const int n = row_mask_count(sp, table, S, max_pred);
+
+  const uint64_t index = static_cast<uint64_t>(sample_index[b]);
+  const uint32_t c2 = static_cast<uint32_t>(index);
+  const uint32_t c3 =
+      (static_cast<uint32_t>(index >> 32) & 0x7FFFFFFFu) | 0x80000000u;
+  const Philox philox(seed);
+  const int64_t row = static_cast<int64_t>(b) * S;
+
+  int32_t id_r[kMaskPerThread];
+  uint32_t w1_r[kMaskPerThread], w2_r[kMaskPerThread];
+  bool cand_r[kMaskPerThread], cont_r[kMaskPerThread], sel_r[kMaskPerThread];
+
+  // 1. draw, as the token-level kernel does; a candidate whose id the table
+  // marks may continue a word. Positions at and above S are never candidates.
+#pragma unroll
+  for (int k = 0; k < kMaskPerThread; ++k) {
+    const int j = k * kMaskThreads + tid;
+    const bool cand = j < last && j != s0 && j != s1;  // last < S
+    const int32_t id = j < S ? ids[row + j] : 0;
+    uint64_t key = ~uint64_t{0};
+    w1_r[k] = w2_r[k] = 0;
+    if (cand) {
+      uint32_t w[4];
+      philox.words(static_cast<uint32_t>(j), epoch, c2, c3, w);
+      key = (static_cast<uint64_t>(w[0]) << 32) | static_cast<uint32_t>(j);
+      w1_r[k] = w[1];
+      w2_r[k] = w[2];
+    }
+    id_r[k] = id;
+    cand_r[k] = cand;
+    cont_r[k] = cand && static_cast<uint32_t>(id) < vocab_size &&
+                word_continues[id] == 1;
+    keys[j] = key;
+    word_sel[j] = 0;
+    const uint64_t cmask = __ballot(cand);
+    if (lane == 0) cand_bits[j >> 6] = cmask;
+  }
+  __syncthreads();
+
+  // 2. word starts: a candidate that does not continue a candidate. A break
+  // is a start or a non-candidate; only starts keep their key.
+#pragma unroll
+  for (int k = 0; k < kMaskPerThread; ++k) {
+    const int j = k * kMaskThreads + tid;
+    const bool prev_cand =
+        j > 0 && ((cand_bits[(j - 1) >> 6] >> ((j - 1) & 63)) & 1) != 0;
+    const bool start = cand_r[k] && !(cont_r[k] && prev_cand);
+    if (cand_r[k] && !start) keys[j] = ~uint64_t{0};
+    cont_r[k] = start;  // from here on: this position starts a word
+    const uint64_t smask = __ballot(start);
+    if (lane == 0) {
+      start_bits[j >> 6] = smask;
+      break_bits[j >> 6] = ~cand_bits[j >> 6] | smask;
+    }
+  }
+  __syncthreads();
+
+  // 3. a word's length is the distance to the next break (position `last`
+  // is one); its rank is the number of smaller keys (keys are distinct: the
+  // position is their low word). The words go to `order` by rank.
+#pragma unroll
+  for (int k = 0; k < kMaskPerThread; ++k) {
+    const int j = k * kMaskThreads + tid;
+    if (cont_r[k] && n > 0) {
+      const uint64_t key = keys[j];
+      const int len = next_set_after(break_bits, j) - j;
+      int rank = 0;
+      for (int i = 0; i < S; ++i) rank += keys[i] < key ? 1 : 0;
+      order[rank] = static_cast<uint32_t>(j) | static_cast<uint32_t>(len) << 16;
+    }
+  }
+  __syncthreads();
+
+  // 4. greedy fill on the first wave, 64 words of the list at a time. While
+  // words are skipped the room left does not change, so the next word taken
+  // is the first pending one that fits: one step per selected word.
+  if (tid < WAVE_SIZE && n > 0) {
+    int words = 0;
+#pragma unroll
+    for (int w = 0; w < kMaskWords; ++w) words += __popcll(start_bits[w]);
+    int m = 0;
+    for (int c = 0; c < words && m < n; c += WAVE_SIZE) {
+      const bool valid = c + lane < words;
+      const uint32_t entry = valid ? order[c + lane] : 0;
+      const int len = static_cast<int>(entry >> 16);
+      bool take = false;
+      uint64_t pending = ~uint64_t{0};
+      while (true) {
+        const uint64_t fits = __ballot(valid && len <= n - m) & pending;
+        if (fits == 0) break;
+        const int pick = __builtin_ctzll(fits);
+        if (lane == pick) take = true;
+        m += __builtin_amdgcn_readlane(len, pick);
+        pending = pick == 63 ? 0 : ~uint64_t{0} << (pick + 1);
+      }
+      if (take) word_sel[entry & 0xFFFFu] = 1;
+    }
+  }
+  __syncthreads();
+
+  // 5. a candidate is selected with the word it belongs to
+#pragma unroll
+  for (int k = 0; k < kMaskPerThread; ++k) {
+    const int j = k * kMaskThreads + tid;
+    bool sel = false;
+    if (cand_r[k]) {
+      const int head = last_set_upto(start_bits, j);
+      sel = head >= 0 && word_sel[head] != 0;
+    }
+    sel_r[k] = sel;
+    const uint64_t mask = __ballot(sel);
+    if (lane == 0) sel_bits[j >> 6] = mask;
+  }
+  __syncthreads();
+
+  // 6. write the row; a selected position also joins the row's compact
+  // list, in ascending position order (at most n <= max_pred entries)
+#pragma unroll
+  for (int k = 0; k < kMaskPerThread; ++k) {
+    const int j = k * kMaskThreads + tid;
+    if (j >= S) continue;
+    int64_t id = id_r[k];
+    int64_t label = -1;
+    if (sel_r[k]) {
+      label = id;
+      const uint64_t w1 = w1_r[k];
+      if (w1 < t_keep) {
+        // keep the original token
+      } else if (w1 < t_keep_rand) {
+        id = static_cast<int64_t>(
+            (static_cast<uint64_t>(w2_r[k]) * (vocab_size - 1)) >> 32);
+      } else {
+        id = mask_token;
+      }
+      int before = __popcll(sel_bits[j >> 6] & ((uint64_t{1} << (j & 63)) - 1));
+      for (int w = 0; w < (j >> 6); ++w) before += __popcll(sel_bits[w]);
+      if (before < max_pred) {
+        row_pos[b * max_pred + before] = static_cast<int32_t>(row + j);
+        row_label[b * max_pred + before] = static_cast<int32_t>(label);
+      }
+    }
+    out_ids[row + j] = id;
+    out_tt[row + j] = (j > s1 && j <= s2) ? 1 : 0;
+    out_am[row + j] = j <= last ? 1 : 0;
+    if (dense != nullptr) dense[row + j] = label;
+  }
+  if (tid == 0) {
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < kMaskWords; ++w) total += __popcll(sel_bits[w]);
+    row_count[b] = total;
+  }
+}
+
+// Row b's first slot is the sum of the counts of the rows before it (strided
+// over the block, wave shuffle + LDS sum); its compact list moves there, and
+// the last block fills the slots no row used.
+__global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_scatter_kernel(
+    const int32_t* __restrict__ row_count, const int32_t* __restrict__ row_pos,
+    const int32_t* __restrict__ row_label, int64_t* __restrict__ positions,
+    int64_t* __restrict__ gathered, int B, int max_pred) {
+  __shared__ int wave_sums[kMaskThreads / WAVE_SIZE];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+
+  int part = 0;
+  for (int r = tid; r < b; r += kMaskThreads)
+    part += min(max(row_count[r], 0), max_pred);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE_SIZE);
+  if ((tid & (WAVE_SIZE - 1)) == 0) wave_sums[tid / WAVE_SIZE] = part;
+  __syncthreads();
+  int base = 0;
+#pragma unroll
+  for (int w = 0; w < kMaskThreads / WAVE_SIZE; ++w) base += wave_sums[w];
+
+  const int count = min(max(row_count[b], 0), max_pred);
+  for (int i = tid; i < count; i += kMaskThreads) {
+    positions[base + i] = row_pos[b * max_pred + i];  // base + i < B * max_pred
+    gathered[base + i] = row_label[b * max_pred + i];
+  }
+  if (b == B - 1) {
+    const int cap = B * max_pred;
+    for (int s = base + count + tid; s < cap; s += kMaskThreads) {
+      positions[s] = 0;
+      gathered[s] = -1;
+    }
+  }
+}
+
 }  // namespace
 
-std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
-                                    torch::Tensor special,
-                                    torch::Tensor sample_index,
-                                    torch::Tensor count_table, int64_t seed,
-                                    int64_t epoch, int64_t max_pred,
-                                    int64_t vocab_size, int64_t mask_token,
-                                    int64_t t_keep, int64_t t_rand,
-                                    bool dense_labels) {
+namespace {
+
+// The argument checks both entry points share, and their outputs:
+// {masked_ids, token_type_ids, attention_mask, positions, gathered_labels
+// (, dense labels)}.
+std::vector<torch::Tensor> checked_mask_outputs(
+    const torch::Tensor& input_ids, const torch::Tensor& special,
+    const torch::Tensor& sample_index, const torch::Tensor& count_table,
+    int64_t max_pred, int64_t vocab_size, int64_t mask_token, int64_t t_keep,
+    int64_t t_rand, bool dense_labels) {
   TORCH_CHECK(input_ids.is_cuda() && input_ids.dim() == 2 &&
                   input_ids.scalar_type() == torch::kInt32,
               "mlm_mask: input_ids must be a 2D int32 GPU tensor, got ",
@@ -208,18 +462,28 @@ std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
   TORCH_CHECK(B * S < (int64_t{1} << 31), "mlm_mask: batch too large");
 
   auto opts = input_ids.options().dtype(torch::kInt64);
-  auto out_ids = torch::empty({B, S}, opts);
-  auto out_tt = torch::empty({B, S}, opts);
-  auto out_am = torch::empty({B, S}, opts);
-  auto positions = torch::empty({B * max_pred}, opts);
-  auto gathered = torch::empty({B * max_pred}, opts);
-  std::vector<torch::Tensor> out = {out_ids, out_tt, out_am, positions,
-                                    gathered};
-  torch::Tensor dense;
-  if (dense_labels) {
-    dense = torch::empty({B, S}, opts);
-    out.push_back(dense);
-  }
+  std::vector<torch::Tensor> out = {
+      torch::empty({B, S}, opts), torch::empty({B, S}, opts),
+      torch::empty({B, S}, opts), torch::empty({B * max_pred}, opts),
+      torch::empty({B * max_pred}, opts)};
+  if (dense_labels) out.push_back(torch::empty({B, S}, opts));
+  return out;
+}
+
+}  // namespace
+
+std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
+                                    torch::Tensor special,
+                                    torch::Tensor sample_index,
+                                    torch::Tensor count_table, int64_t seed,
+                                    int64_t epoch, int64_t max_pred,
+                                    int64_t vocab_size, int64_t mask_token,
+                                    int64_t t_keep, int64_t t_rand,
+                                    bool dense_labels) {
+  auto out = checked_mask_outputs(input_ids, special, sample_index,
+                                  count_table, max_pred, vocab_size,
+                                  mask_token, t_keep, t_rand, dense_labels);
+  const int64_t B = input_ids.size(0), S = input_ids.size(1);
   if (B == 0) return out;
 
   auto stream = at::hip::getCurrentHIPStream();
@@ -227,14 +491,63 @@ std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
       mlm_mask_kernel, dim3(static_cast<uint32_t>(B)), dim3(kMaskThreads), 0,
       stream, input_ids.data_ptr<int32_t>(), special.data_ptr<int32_t>(),
       sample_index.data_ptr<int64_t>(), count_table.data_ptr<int32_t>(),
-      out_ids.data_ptr<int64_t>(), out_tt.data_ptr<int64_t>(),
-      out_am.data_ptr<int64_t>(), positions.data_ptr<int64_t>(),
-      gathered.data_ptr<int64_t>(),
-      dense_labels ? dense.data_ptr<int64_t>() : nullptr, static_cast<int>(B),
+      out[0].data_ptr<int64_t>(), out[1].data_ptr<int64_t>(),
+      out[2].data_ptr<int64_t>(), out[3].data_ptr<int64_t>(),
+      out[4].data_ptr<int64_t>(),
+      dense_labels ? out[5].data_ptr<int64_t>() : nullptr, static_cast<int>(B),
       static_cast<int>(S), static_cast<int>(max_pred),
       static_cast<uint64_t>(seed), static_cast<uint32_t>(epoch),
       static_cast<uint32_t>(vocab_size - 1), mask_token,
       static_cast<uint64_t>(t_keep), static_cast<uint64_t>(t_keep + t_rand));
+  HIP_CHECK(hipGetLastError());
+  return out;
+}
+
+std::vector<torch::Tensor> mlm_mask_whole_word(
+    torch::Tensor input_ids, torch::Tensor special, torch::Tensor sample_index,
+    torch::Tensor count_table, torch::Tensor word_continues, int64_t seed,
+    int64_t epoch, int64_t max_pred, int64_t vocab_size, int64_t mask_token,
+    int64_t t_keep, int64_t t_rand, bool dense_labels) {
+  auto out = checked_mask_outputs(input_ids, special, sample_index,
+                                  count_table, max_pred, vocab_size,
+                                  mask_token, t_keep, t_rand, dense_labels);
+  TORCH_CHECK(word_continues.device() == input_ids.device() &&
+                  word_continues.scalar_type() == torch::kUInt8 &&
+                  word_continues.dim() == 1 &&
+                  word_continues.size(0) == vocab_size &&
+                  word_continues.is_contiguous(),
+              "mlm_mask: word_continues must be contiguous uint8 [",
+              vocab_size, "] on the device of input_ids, got ",
+              word_continues.scalar_type(), " ", word_continues.sizes());
+  const int64_t B = input_ids.size(0), S = input_ids.size(1);
+  if (B == 0) return out;
+
+  // per row: its count, then max_pred positions and max_pred labels
+  auto scratch = torch::empty({B * (2 * max_pred + 1)},
+                              input_ids.options().dtype(torch::kInt32));
+  int32_t* row_count = scratch.data_ptr<int32_t>();
+  int32_t* row_pos = row_count + B;
+  int32_t* row_label = row_pos + B * max_pred;
+
+  auto stream = at::hip::getCurrentHIPStream();
+  hipLaunchKernelGGL(
+      mlm_mask_wwm_select_kernel, dim3(static_cast<uint32_t>(B)),
+      dim3(kMaskThreads), 0, stream, input_ids.data_ptr<int32_t>(),
+      special.data_ptr<int32_t>(), sample_index.data_ptr<int64_t>(),
+      count_table.data_ptr<int32_t>(), word_continues.data_ptr<uint8_t>(),
+      out[0].data_ptr<int64_t>(), out[1].data_ptr<int64_t>(),
+      out[2].data_ptr<int64_t>(),
+      dense_labels ? out[5].data_ptr<int64_t>() : nullptr, row_count, row_pos,
+      row_label, static_cast<int>(S), static_cast<int>(max_pred),
+      static_cast<uint64_t>(seed), static_cast<uint32_t>(epoch),
+      static_cast<uint32_t>(vocab_size), mask_token,
+      static_cast<uint64_t>(t_keep), static_cast<uint64_t>(t_keep + t_rand));
+  HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(mlm_mask_wwm_scatter_kernel,
+                     dim3(static_cast<uint32_t>(B)), dim3(kMaskThreads), 0,
+                     stream, row_count, row_pos, row_label,
+                     out[3].data_ptr<int64_t>(), out[4].data_ptr<int64_t>(),
+                     static_cast<int>(B), static_cast<int>(max_pred));
   HIP_CHECK(hipGetLastError());
   return out;
 }

@@ -102,6 +102,14 @@ def parse_arguments(args=None) -> argparse.Namespace:
                              "sample index) only, not on --num_workers, the "
                              "world size or a resume; needs unmasked shards; "
                              "evaluation keeps its static CPU masks")
+    parser.add_argument("--whole_word_masking", action="store_true",
+                        help="mask whole words in the training batches: all "
+                             "pieces of a word or none (## pieces of a "
+                             "WordPiece vocabulary, non-Ġ pieces of a "
+                             "byte-level BPE one); needs --vocab_file and "
+                             "unmasked shards; works with and without "
+                             "--device_masking; evaluation keeps its static "
+                             "token-level masks")
     parser.add_argument("--vocab_file", type=str, default=None)
     parser.add_argument("--mask_token_index", type=int, default=None)
     parser.add_argument("--vocab_pad_multiple", type=int, default=64,
@@ -136,8 +144,15 @@ def parse_arguments(args=None) -> argparse.Namespace:
     ns = merge_config_and_args(parser, args)
     # bool-ish JSON values
     for key in ("fp16", "bf16", "bf16_weights", "kfac", "disable_progress_bar",
-                "checkpoint_activations", "unpad", "device_masking"):
+                "checkpoint_activations", "unpad", "device_masking",
+                "whole_word_masking"):
         setattr(ns, key, bool(getattr(ns, key)))
+    if ns.whole_word_masking and not ns.vocab_file:
+        raise ValueError(
+            "--whole_word_masking needs --vocab_file: which vocabulary "
+            "entries continue a word is read from the vocabulary. Give the "
+            "vocabulary the shards were encoded with, or drop the flag."
+        )
     if ns.unpad and ns.kfac:
         raise ValueError(
             "--unpad cannot be combined with --kfac: the K-FAC factor hooks "
@@ -331,12 +346,28 @@ def _mask_index_and_vocab(args):
     return mask_index, vocab_size
 
 
+def _word_continues(args, vocab_size):
+    """--whole_word_masking: the uint8 [vocab_size] table of the
+    vocabulary entries that continue a word; None without the flag."""
+    if not args.whole_word_masking:
+        return None
+    if not os.path.isfile(args.vocab_file):
+        raise ValueError(
+            f"--whole_word_masking: --vocab_file {args.vocab_file} does not "
+            "exist"
+        )
+    from bert_pytorch_amd.data.tokenization import word_continuation_table  # noqa: PLC0415
+
+    return word_continuation_table(args.vocab_file, vocab_size)
+
+
 def prepare_dataset(args, resume_state):
     files = sorted(str(p) for p in Path(args.input_dir).rglob("*.hdf5"))
     if not files:
         raise RuntimeError(f"no *.hdf5 shards under {args.input_dir}")
 
     mask_index, vocab_size = _mask_index_and_vocab(args)
+    whole_word = args.whole_word_masking and not args.device_masking
 
     dataset = ShardedPretrainingDataset(
         files,
@@ -346,6 +377,8 @@ def prepare_dataset(args, resume_state):
         vocab_size=vocab_size,
         seed=args.seed,
         device_masking=args.device_masking,
+        whole_word_masking=whole_word,
+        word_continues=_word_continues(args, vocab_size) if whole_word else None,
     )
     sampler = DistributedSampler(
         dataset, comm.get_world_size(), rank=comm.get_rank(), seed=args.seed
@@ -376,6 +409,7 @@ def prepare_masker(args):
         max_pred_per_seq=args.max_predictions_per_seq,
         masked_lm_prob=args.masked_token_fraction,
         vocab_size=vocab_size,
+        word_continues=_word_continues(args, vocab_size),
     )
 
 
