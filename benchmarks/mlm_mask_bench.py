@@ -14,7 +14,7 @@ contender once (device events around ITERS back-to-back calls) and the
 table reports the median over rounds with the min-max spread.
 
 ``--whole_word`` times whole-word masking instead of the gather:
-  wwm     ops.mlm_mask(..., word_continues=table): the selection kernel
+  wwm     ops.mlm_mask(..., word_continues=table): the whole-word row kernel
           and the scatter kernel, two launches, on the same rows, with a
           table that marks a fifth of the vocabulary as continuation pieces
 

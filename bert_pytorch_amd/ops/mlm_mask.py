@@ -76,41 +76,6 @@ def _signed64(value: int) -> int:
     return value - (1 << 64) if value >= 1 << 63 else value
 
 
-def _mlm_mask_whole_word(
-    input_ids, special, sample_index, count_table, word_continues, seed,
-    epoch, max_pred, vocab_size, mask_token, t_keep, t_rand, dense_labels,
-):
-    if use_native(input_ids):
-        out = extension().mlm_mask_whole_word(
-            input_ids, special.contiguous(), sample_index, count_table,
-            word_continues, _signed64(seed), epoch & 0xFFFFFFFF, max_pred,
-            vocab_size, mask_token, t_keep, t_rand, dense_labels,
-        )
-        return (*out[:5], out[5] if dense_labels else None)
-    seq = input_ids.shape[1]
-    if not (1 <= max_pred <= seq and count_table.numel() == seq + 1):
-        raise ValueError(
-            f"need 1 <= max_pred ({max_pred}) <= S ({seq}) and a count "
-            f"table of S + 1 entries, got {count_table.numel()}"
-        )
-    if (
-        word_continues.device != input_ids.device
-        or word_continues.dtype != torch.uint8
-        or word_continues.dim() != 1
-        or word_continues.numel() != vocab_size
-    ):
-        raise ValueError(
-            f"word_continues must be uint8 [{vocab_size}] on the device of "
-            f"input_ids, got {word_continues.dtype} "
-            f"{tuple(word_continues.shape)} on {word_continues.device}"
-        )
-    out = _reference.mlm_mask_whole_word(
-        input_ids, special, sample_index, count_table, word_continues, seed,
-        epoch, max_pred, vocab_size, mask_token, t_keep, t_rand,
-    )
-    return (*out[:5], out[5] if dense_labels else None)
-
-
 def mlm_mask(
     input_ids: torch.Tensor,
     special: torch.Tensor,
@@ -149,27 +114,43 @@ def mlm_mask(
         raise ValueError("special must be [B, 2] or [B, 3]")
     if special.shape[1] == 2:
         special = torch.cat([special, special[:, 1:]], dim=1)
-    if word_continues is not None:
-        return _mlm_mask_whole_word(
-            input_ids, special, sample_index, count_table, word_continues,
-            seed, epoch, max_pred, vocab_size, mask_token, t_keep, t_rand,
-            dense_labels,
-        )
     if use_native(input_ids):
-        out = extension().mlm_mask(
-            input_ids, special.contiguous(), sample_index, count_table,
-            _signed64(seed), epoch & 0xFFFFFFFF, max_pred, vocab_size,
-            mask_token, t_keep, t_rand, dense_labels,
-        )
-        return (*out[:5], out[5] if dense_labels else None)
-    seq = input_ids.shape[1]
-    if not (1 <= max_pred <= seq and count_table.numel() == seq + 1):
-        raise ValueError(
-            f"need 1 <= max_pred ({max_pred}) <= S ({seq}) and a count "
-            f"table of S + 1 entries, got {count_table.numel()}"
-        )
-    out = _reference.mlm_mask(
-        input_ids, special, sample_index, count_table, seed, epoch, max_pred,
-        vocab_size, mask_token, t_keep, t_rand,
-    )
+        # spelled out twice: on the hot path a call costs less than building
+        # and unpacking argument tuples
+        if word_continues is None:
+            out = extension().mlm_mask(
+                input_ids, special.contiguous(), sample_index, count_table,
+                _signed64(seed), epoch & 0xFFFFFFFF, max_pred, vocab_size,
+                mask_token, t_keep, t_rand, dense_labels,
+            )
+        else:
+            out = extension().mlm_mask_whole_word(
+                input_ids, special.contiguous(), sample_index, count_table,
+                word_continues, _signed64(seed), epoch & 0xFFFFFFFF, max_pred,
+                vocab_size, mask_token, t_keep, t_rand, dense_labels,
+            )
+    else:
+        seq = input_ids.shape[1]
+        if not (1 <= max_pred <= seq and count_table.numel() == seq + 1):
+            raise ValueError(
+                f"need 1 <= max_pred ({max_pred}) <= S ({seq}) and a count "
+                f"table of S + 1 entries, got {count_table.numel()}"
+            )
+        head = (input_ids, special, sample_index, count_table)
+        tail = (seed, epoch, max_pred, vocab_size, mask_token, t_keep, t_rand)
+        if word_continues is None:
+            out = _reference.mlm_mask(*head, *tail)
+        else:
+            if (
+                word_continues.device != input_ids.device
+                or word_continues.dtype != torch.uint8
+                or word_continues.dim() != 1
+                or word_continues.numel() != vocab_size
+            ):
+                raise ValueError(
+                    f"word_continues must be uint8 [{vocab_size}] on the "
+                    f"device of input_ids, got {word_continues.dtype} "
+                    f"{tuple(word_continues.shape)} on {word_continues.device}"
+                )
+            out = _reference.mlm_mask_whole_word(*head, word_continues, *tail)
     return (*out[:5], out[5] if dense_labels else None)

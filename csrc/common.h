@@ -142,29 +142,13 @@ struct Philox {
   static __device__ __forceinline__ uint32_t mulhi(uint32_t a, uint32_t b) {
     return static_cast<uint32_t>((static_cast<uint64_t>(a) * b) >> 32);
   }
-  // returns 4 uniform u32 for counter `ctr`
+  // returns 4 uniform u32 for counter `ctr`: c2 = c3 = 0, so a full counter
+  // with c3 != 0 never meets a dropout counter
   __device__ __forceinline__ void operator()(uint64_t ctr, uint32_t out[4]) const {
-    uint32_t c0 = static_cast<uint32_t>(ctr);
-    uint32_t c1 = static_cast<uint32_t>(ctr >> 32);
-    uint32_t c2 = 0, c3 = 0;
-    uint32_t key0 = k0, key1 = k1;
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-    constexpr uint32_t W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-      uint32_t hi0 = mulhi(M0, c0), lo0 = M0 * c0;
-      uint32_t hi1 = mulhi(M1, c2), lo1 = M1 * c2;
-      uint32_t n0 = hi1 ^ c1 ^ key0;
-      uint32_t n1 = lo1;
-      uint32_t n2 = hi0 ^ c3 ^ key1;
-      uint32_t n3 = lo0;
-      c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-      key0 += W0; key1 += W1;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+    words(static_cast<uint32_t>(ctr), static_cast<uint32_t>(ctr >> 32), 0, 0,
+          out);
   }
-  // the same ten rounds on a full 4-word counter (c2, c3 are zero above, so
-  // a counter with c3 != 0 never meets a dropout counter)
+  // Philox4x32-10 on a full 4-word counter
   __device__ __forceinline__ void words(uint32_t c0, uint32_t c1, uint32_t c2,
                                         uint32_t c3, uint32_t out[4]) const {
     uint32_t key0 = k0, key1 = k1;

@@ -1,30 +1,38 @@
 // Dynamic MLM masking on the device: raw shard rows in, model inputs and the
-// padded-gather MLM positions out, in one launch.
+// padded-gather MLM positions out. Nothing is read back to the host, there is
+// no atomic and no waiting between workgroups.
 //
 // The mask of a row is a pure function of (seed, epoch, sample index,
 // position): every candidate position j draws Philox4x32-10 words at the
 // counter (j, epoch, lo32(index), hi32(index) | 2^31) under the key `seed`,
 // the n candidates with the smallest (w0 << 32 | j) are selected, and w1 / w2
 // decide keep / random token / mask token. docs/KERNELS.md has the full
-// definition; tests/test_gpu_mlm_mask.py holds a numpy twin the kernel is
-// bit-equal to.
+// definition; tests/mlm_mask_spec.py holds the numpy and plain-Python twins
+// the kernel is bit-equal to.
 //
-// One workgroup per row. A row's first output slot is the number of masked
-// tokens in the rows before it, which every block recomputes from the
-// `special` entries of those rows (three integers and a table lookup per
-// row), so there is no communication between workgroups and no atomic. The
-// last block also fills the unused tail of the slot budget. Nothing is read
-// back to the host.
+// One row kernel, mlm_mask_row_kernel<WHOLE_WORD>: one workgroup of 256
+// threads per row. Position j belongs to thread j % 256 in every phase, so
+// what a position draws stays in that thread's registers, and a wave's
+// ballot is the 64-bit word j / 64 of a row-wide bit mask in LDS. Header,
+// draw, the count-smaller rank, the selected bits, the substitution, the
+// [B,S] stores and a selected position's index among the row's selected
+// (popcounts over the bit mask) are the same code for both instantiations.
+// The template switch changes two things:
 //
-// Whole-word masking (mlm_mask_whole_word) groups the candidates into words
-// with a uint8 [vocab_size] table of continuation pieces, orders the words
-// by the key of their first position and fills the budget greedily, whole
-// words only. A row's count is then no function of its specials, so the
-// work is two launches on one stream: the selection kernel (one workgroup
-// per row) writes the [B,S] outputs, the row's count and its compact list
-// of positions and labels; the scatter kernel sums the counts of the rows
-// before its own and moves the lists to their slots. Still no atomic, no
-// waiting between workgroups and no read-back.
+//   * which candidates are selected. Token-level: the ones of rank < n.
+//     Whole words: a uint8 [vocab_size] table of continuation pieces groups
+//     the candidates into words, the words are ordered by the key of their
+//     first position and fill the budget greedily, whole words only.
+//   * where a row's masked tokens go. Token-level: a row's count is a
+//     function of its specials, so every block recomputes its first slot
+//     from the `special` entries of the rows before it (three integers and a
+//     table lookup per row) and stores to `positions` / `gathered` directly;
+//     the last block fills the unused tail of the slot budget. One launch.
+//     Whole words: the count is known only after the selection, so the row
+//     kernel writes the row's count and a compact list, and
+//     mlm_mask_scatter_kernel, a second launch on the same stream, sums the
+//     counts of the rows before its own, moves the lists to their slots and
+//     fills the tail.
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -37,6 +45,8 @@ namespace {
 
 constexpr int kMaskMaxS = 1024;
 constexpr int kMaskThreads = 256;
+constexpr int kMaskPerThread = kMaskMaxS / kMaskThreads;  // 4
+constexpr int kMaskWords = kMaskMaxS / WAVE_SIZE;         // 16
 
 // Masked tokens of a row, from its specials alone. Candidates are the
 // positions below `last` = clamp(s[2], 0, S-1) that no special names; s[2]
@@ -54,124 +64,42 @@ __device__ __forceinline__ int row_mask_count(const int32_t* __restrict__ s,
   return max(0, min(table[c], min(max_pred, c)));  // 0 <= c <= S-1
 }
 
-__global__ __launch_bounds__(kMaskThreads) void mlm_mask_kernel(
-    const int32_t* __restrict__ ids, const int32_t* __restrict__ special,
-    const int64_t* __restrict__ sample_index,
-    const int32_t* __restrict__ table, int64_t* __restrict__ out_ids,
-    int64_t* __restrict__ out_tt, int64_t* __restrict__ out_am,
-    int64_t* __restrict__ positions, int64_t* __restrict__ gathered,
-    int64_t* __restrict__ dense,  // may be null
-    int B, int S, int max_pred, uint64_t seed, uint32_t epoch,
-    uint32_t vocab_m1, int64_t mask_token, uint64_t t_keep,
-    uint64_t t_keep_rand) {
-  __shared__ uint64_t keys[kMaskMaxS];
-  __shared__ uint32_t w1s[kMaskMaxS];
-  __shared__ uint32_t w2s[kMaskMaxS];
-  __shared__ uint8_t sel[kMaskMaxS];
+// Sum of count(r) over the rows r < rows, on every thread of the block
+// (strided over the block, wave shuffle + LDS sum). Holds one barrier.
+template <typename F>
+__device__ __forceinline__ int block_sum_before(int rows, F count) {
   __shared__ int wave_sums[kMaskThreads / WAVE_SIZE];
-
-  const int b = blockIdx.x;
   const int tid = threadIdx.x;
-
-  // first output slot of this row
   int part = 0;
-  for (int r = tid; r < b; r += kMaskThreads)
-    part += row_mask_count(special + 3 * r, table, S, max_pred);
+  for (int r = tid; r < rows; r += kMaskThreads) part += count(r);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE_SIZE);
   if ((tid & (WAVE_SIZE - 1)) == 0) wave_sums[tid / WAVE_SIZE] = part;
   __syncthreads();
-  int base = 0;
+  int sum = 0;
 #pragma unroll
-  for (int w = 0; w < kMaskThreads / WAVE_SIZE; ++w) base += wave_sums[w];
+  for (int w = 0; w < kMaskThreads / WAVE_SIZE; ++w) sum += wave_sums[w];
+  return sum;
+}
 
-  const int32_t* sp = special + 3 * b;
-  const int s0 = sp[0], s1 = sp[1], s2 = sp[2];
-  const int last = min(max(s2, 0), S - 1);
-  const int n = row_mask_count(sp, table, S, max_pred);
-
-  const uint64_t index = static_cast<uint64_t>(sample_index[b]);
-  const uint32_t c2 = static_cast<uint32_t>(index);
-  const uint32_t c3 =
-      (static_cast<uint32_t>(index >> 32) & 0x7FFFFFFFu) | 0x80000000u;
-  const Philox philox(seed);
-
-  // 1. draw: candidates get their sort key, everything else the maximum
-  for (int j = tid; j < S; j += kMaskThreads) {
-    const bool cand = j < last && j != s0 && j != s1;
-    uint64_t key = ~uint64_t{0};
-    if (cand) {
-      uint32_t w[4];
-      philox.words(static_cast<uint32_t>(j), epoch, c2, c3, w);
-      key = (static_cast<uint64_t>(w[0]) << 32) | static_cast<uint32_t>(j);
-      w1s[j] = w[1];
-      w2s[j] = w[2];
-    }
-    keys[j] = key;
-  }
-  __syncthreads();
-
-  // 2. select: a candidate's rank is the number of smaller keys (keys are
-  // distinct: the position is their low word)
-  for (int j = tid; j < S; j += kMaskThreads) {
-    const uint64_t key = keys[j];
-    bool chosen = false;
-    if (key != ~uint64_t{0} && n > 0) {
-      int rank = 0;
-      for (int i = 0; i < S; ++i) rank += keys[i] < key ? 1 : 0;
-      chosen = rank < n;
-    }
-    sel[j] = chosen ? 1 : 0;
-  }
-  __syncthreads();
-
-  // 3. write the row; a selected position also takes its slot, in
-  // ascending position order
-  const int64_t row = static_cast<int64_t>(b) * S;
-  for (int j = tid; j < S; j += kMaskThreads) {
-    int64_t id = ids[row + j];
-    int64_t label = -1;
-    if (sel[j]) {
-      label = id;
-      const uint64_t w1 = w1s[j];
-      if (w1 < t_keep) {
-        // keep the original token
-      } else if (w1 < t_keep_rand) {
-        id = static_cast<int64_t>(
-            (static_cast<uint64_t>(w2s[j]) * vocab_m1) >> 32);
-      } else {
-        id = mask_token;
-      }
-      int before = 0;
-      for (int i = 0; i < j; ++i) before += sel[i];
-      const int slot = base + before;  // < base + n <= B * max_pred
-      positions[slot] = row + j;
-      gathered[slot] = label;
-    }
-    out_ids[row + j] = id;
-    out_tt[row + j] = (j > s1 && j <= s2) ? 1 : 0;
-    out_am[row + j] = j <= last ? 1 : 0;
-    if (dense != nullptr) dense[row + j] = label;
-  }
-
-  // 4. the slots no row used
-  if (b == B - 1) {
-    const int cap = B * max_pred;
-    for (int s = base + n + tid; s < cap; s += kMaskThreads) {
-      positions[s] = 0;
-      gathered[s] = -1;
-    }
+// the slots no row used: [first, cap)
+__device__ __forceinline__ void fill_unused_slots(
+    int64_t* __restrict__ positions, int64_t* __restrict__ gathered, int first,
+    int cap) {
+  for (int s = first + threadIdx.x; s < cap; s += kMaskThreads) {
+    positions[s] = 0;
+    gathered[s] = -1;
   }
 }
 
-// ---------------------------------------------------------------------------
-// whole-word masking
-// ---------------------------------------------------------------------------
-// Position j of a row belongs to thread j % 256 in every phase, so what a
-// position draws stays in that thread's registers, and a wave's ballot is
-// the 64-bit word j / 64 of a row-wide bit mask in LDS.
-constexpr int kMaskPerThread = kMaskMaxS / kMaskThreads;  // 4
-constexpr int kMaskWords = kMaskMaxS / WAVE_SIZE;         // 16
+// A key's rank is the number of smaller keys (keys are distinct: the
+// position is their low word).
+__device__ __forceinline__ int count_smaller(const uint64_t* keys, int S,
+                                             uint64_t key) {
+  int rank = 0;
+  for (int i = 0; i < S; ++i) rank += keys[i] < key ? 1 : 0;
+  return rank;
+}
 
 // first set bit above position j, kMaskMaxS if there is none
 __device__ __forceinline__ int next_set_after(const uint64_t* bits, int j) {
@@ -189,33 +117,43 @@ __device__ __forceinline__ int last_set_upto(const uint64_t* bits, int j) {
   return m != 0 ? (w << 6) + 63 - __builtin_clzll(m) : -1;
 }
 
-__global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_select_kernel(
+// WHOLE_WORD reads word_continues and writes row_count / row_pos / row_label;
+// token-level reads `special` of the rows before and writes positions /
+// gathered. The pointers of the other instantiation are never touched.
+template <bool WHOLE_WORD>
+__global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
     const int32_t* __restrict__ ids, const int32_t* __restrict__ special,
     const int64_t* __restrict__ sample_index,
     const int32_t* __restrict__ table,
     const uint8_t* __restrict__ word_continues, int64_t* __restrict__ out_ids,
     int64_t* __restrict__ out_tt, int64_t* __restrict__ out_am,
     int64_t* __restrict__ dense,  // may be null
+    int64_t* __restrict__ positions, int64_t* __restrict__ gathered,
     int32_t* __restrict__ row_count, int32_t* __restrict__ row_pos,
-    int32_t* __restrict__ row_label, int S, int max_pred, uint64_t seed,
+    int32_t* __restrict__ row_label, int B, int S, int max_pred, uint64_t seed,
     uint32_t epoch, uint32_t vocab_size, int64_t mask_token, uint64_t t_keep,
     uint64_t t_keep_rand) {
   __shared__ uint64_t keys[kMaskMaxS];
-  __shared__ uint32_t order[kMaskMaxS];  // first | len << 16, by rank
-  __shared__ uint8_t word_sel[kMaskMaxS];
-  __shared__ uint64_t cand_bits[kMaskWords];
-  __shared__ uint64_t start_bits[kMaskWords];
-  __shared__ uint64_t break_bits[kMaskWords];
   __shared__ uint64_t sel_bits[kMaskWords];
 
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE_SIZE - 1);
 
+  // token-level: first output slot of this row
+  int base = 0;
+  if constexpr (!WHOLE_WORD) {
+    base = block_sum_before(b, [&](int r) {
+      return row_mask_count(special + 3 * r, table, S, max_pred);
+    });
+  }
+
   const int32_t* sp = special + 3 * b;
   const int s0 = sp[0], s1 = sp[1], s2 = sp[2];
   const int last = min(max(s2, 0), S - 1);
   const int n = row_mask_count(sp, table, S, max_pred);
+  // positions at and above S are never candidates: last < S
+  auto is_cand = [&](int j) { return j < last && j != s0 && j != s1; };
 
   const uint64_t index = static_cast<uint64_t>(sample_index[b]);
   const uint32_t c2 = static_cast<uint32_t>(index);
@@ -226,15 +164,13 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_select_kernel(
 
   int32_t id_r[kMaskPerThread];
   uint32_t w1_r[kMaskPerThread], w2_r[kMaskPerThread];
-  bool cand_r[kMaskPerThread], cont_r[kMaskPerThread], sel_r[kMaskPerThread];
+  bool cand_r[kMaskPerThread], sel_r[kMaskPerThread];
 
-  // 1. draw, as the token-level kernel does; a candidate whose id the table
-  // marks may continue a word. Positions at and above S are never candidates.
+  // draw: candidates get their sort key, everything else the maximum
 #pragma unroll
   for (int k = 0; k < kMaskPerThread; ++k) {
     const int j = k * kMaskThreads + tid;
-    const bool cand = j < last && j != s0 && j != s1;  // last < S
-    const int32_t id = j < S ? ids[row + j] : 0;
+    const bool cand = is_cand(j);
     uint64_t key = ~uint64_t{0};
     w1_r[k] = w2_r[k] = 0;
     if (cand) {
@@ -244,95 +180,111 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_select_kernel(
       w1_r[k] = w[1];
       w2_r[k] = w[2];
     }
-    id_r[k] = id;
+    id_r[k] = j < S ? ids[row + j] : 0;
     cand_r[k] = cand;
-    cont_r[k] = cand && static_cast<uint32_t>(id) < vocab_size &&
-                word_continues[id] == 1;
     keys[j] = key;
-    word_sel[j] = 0;
-    const uint64_t cmask = __ballot(cand);
-    if (lane == 0) cand_bits[j >> 6] = cmask;
   }
-  __syncthreads();
 
-  // 2. word starts: a candidate that does not continue a candidate. A break
-  // is a start or a non-candidate; only starts keep their key.
-#pragma unroll
-  for (int k = 0; k < kMaskPerThread; ++k) {
-    const int j = k * kMaskThreads + tid;
-    const bool prev_cand =
-        j > 0 && ((cand_bits[(j - 1) >> 6] >> ((j - 1) & 63)) & 1) != 0;
-    const bool start = cand_r[k] && !(cont_r[k] && prev_cand);
-    if (cand_r[k] && !start) keys[j] = ~uint64_t{0};
-    cont_r[k] = start;  // from here on: this position starts a word
-    const uint64_t smask = __ballot(start);
-    if (lane == 0) {
-      start_bits[j >> 6] = smask;
-      break_bits[j >> 6] = ~cand_bits[j >> 6] | smask;
-    }
-  }
-  __syncthreads();
+  if constexpr (WHOLE_WORD) {
+    __shared__ uint32_t order[kMaskMaxS];  // first | len << 16, by rank
+    __shared__ uint8_t word_sel[kMaskMaxS];
+    __shared__ uint64_t start_bits[kMaskWords];
+    __shared__ uint64_t break_bits[kMaskWords];
+    bool start_r[kMaskPerThread];
 
-  // 3. a word's length is the distance to the next break (position `last`
-  // is one); its rank is the number of smaller keys (keys are distinct: the
-  // position is their low word). The words go to `order` by rank.
+    // word starts: a candidate that does not continue a candidate (an id
+    // outside the table continues nothing). A break is a start or a
+    // non-candidate; only starts keep their key.
 #pragma unroll
-  for (int k = 0; k < kMaskPerThread; ++k) {
-    const int j = k * kMaskThreads + tid;
-    if (cont_r[k] && n > 0) {
-      const uint64_t key = keys[j];
-      const int len = next_set_after(break_bits, j) - j;
-      int rank = 0;
-      for (int i = 0; i < S; ++i) rank += keys[i] < key ? 1 : 0;
-      order[rank] = static_cast<uint32_t>(j) | static_cast<uint32_t>(len) << 16;
-    }
-  }
-  __syncthreads();
-
-  // 4. greedy fill on the first wave, 64 words of the list at a time. While
-  // words are skipped the room left does not change, so the next word taken
-  // is the first pending one that fits: one step per selected word.
-  if (tid < WAVE_SIZE && n > 0) {
-    int words = 0;
-#pragma unroll
-    for (int w = 0; w < kMaskWords; ++w) words += __popcll(start_bits[w]);
-    int m = 0;
-    for (int c = 0; c < words && m < n; c += WAVE_SIZE) {
-      const bool valid = c + lane < words;
-      const uint32_t entry = valid ? order[c + lane] : 0;
-      const int len = static_cast<int>(entry >> 16);
-      bool take = false;
-      uint64_t pending = ~uint64_t{0};
-      while (true) {
-        const uint64_t fits = __ballot(valid && len <= n - m) & pending;
-        if (fits == 0) break;
-        const int pick = __builtin_ctzll(fits);
-        if (lane == pick) take = true;
-        m += __builtin_amdgcn_readlane(len, pick);
-        pending = pick == 63 ? 0 : ~uint64_t{0} << (pick + 1);
+    for (int k = 0; k < kMaskPerThread; ++k) {
+      const int j = k * kMaskThreads + tid;
+      const bool continues = cand_r[k] &&
+                             static_cast<uint32_t>(id_r[k]) < vocab_size &&
+                             word_continues[id_r[k]] == 1;
+      const bool start = cand_r[k] && !(continues && j > 0 && is_cand(j - 1));
+      if (cand_r[k] && !start) keys[j] = ~uint64_t{0};
+      start_r[k] = start;
+      word_sel[j] = 0;
+      const uint64_t cmask = __ballot(cand_r[k]);
+      const uint64_t smask = __ballot(start);
+      if (lane == 0) {
+        start_bits[j >> 6] = smask;
+        break_bits[j >> 6] = ~cmask | smask;
       }
-      if (take) word_sel[entry & 0xFFFFu] = 1;
+    }
+    __syncthreads();
+
+    // a word's length is the distance to the next break (position `last`
+    // is one). The words go to `order` by the rank of their key.
+#pragma unroll
+    for (int k = 0; k < kMaskPerThread; ++k) {
+      const int j = k * kMaskThreads + tid;
+      if (start_r[k] && n > 0) {
+        const int len = next_set_after(break_bits, j) - j;
+        order[count_smaller(keys, S, keys[j])] =
+            static_cast<uint32_t>(j) | static_cast<uint32_t>(len) << 16;
+      }
+    }
+    __syncthreads();
+
+    // greedy fill on the first wave, 64 words of the list at a time. While
+    // words are skipped the room left does not change, so the next word taken
+    // is the first pending one that fits: one step per selected word.
+    if (tid < WAVE_SIZE && n > 0) {
+      int words = 0;
+#pragma unroll
+      for (int w = 0; w < kMaskWords; ++w) words += __popcll(start_bits[w]);
+      int m = 0;
+      for (int c = 0; c < words && m < n; c += WAVE_SIZE) {
+        const bool valid = c + lane < words;
+        const uint32_t entry = valid ? order[c + lane] : 0;
+        const int len = static_cast<int>(entry >> 16);
+        bool take = false;
+        uint64_t pending = ~uint64_t{0};
+        while (true) {
+          const uint64_t fits = __ballot(valid && len <= n - m) & pending;
+          if (fits == 0) break;
+          const int pick = __builtin_ctzll(fits);
+          if (lane == pick) take = true;
+          m += __builtin_amdgcn_readlane(len, pick);
+          pending = pick == 63 ? 0 : ~uint64_t{0} << (pick + 1);
+        }
+        if (take) word_sel[entry & 0xFFFFu] = 1;
+      }
+    }
+    __syncthreads();
+
+    // a candidate is selected with the word it belongs to
+#pragma unroll
+    for (int k = 0; k < kMaskPerThread; ++k) {
+      const int j = k * kMaskThreads + tid;
+      bool sel = false;
+      if (cand_r[k]) {
+        const int head = last_set_upto(start_bits, j);
+        sel = head >= 0 && word_sel[head] != 0;
+      }
+      sel_r[k] = sel;
+    }
+  } else {
+    __syncthreads();
+    // the n candidates with the smallest keys
+#pragma unroll
+    for (int k = 0; k < kMaskPerThread; ++k) {
+      const int j = k * kMaskThreads + tid;
+      sel_r[k] = cand_r[k] && n > 0 && count_smaller(keys, S, keys[j]) < n;
     }
   }
-  __syncthreads();
 
-  // 5. a candidate is selected with the word it belongs to
 #pragma unroll
   for (int k = 0; k < kMaskPerThread; ++k) {
     const int j = k * kMaskThreads + tid;
-    bool sel = false;
-    if (cand_r[k]) {
-      const int head = last_set_upto(start_bits, j);
-      sel = head >= 0 && word_sel[head] != 0;
-    }
-    sel_r[k] = sel;
-    const uint64_t mask = __ballot(sel);
+    const uint64_t mask = __ballot(sel_r[k]);
     if (lane == 0) sel_bits[j >> 6] = mask;
   }
   __syncthreads();
 
-  // 6. write the row; a selected position also joins the row's compact
-  // list, in ascending position order (at most n <= max_pred entries)
+  // write the row; a selected position also takes its place among the row's
+  // selected, in ascending position order (at most n <= max_pred of them)
 #pragma unroll
   for (int k = 0; k < kMaskPerThread; ++k) {
     const int j = k * kMaskThreads + tid;
@@ -352,9 +304,15 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_select_kernel(
       }
       int before = __popcll(sel_bits[j >> 6] & ((uint64_t{1} << (j & 63)) - 1));
       for (int w = 0; w < (j >> 6); ++w) before += __popcll(sel_bits[w]);
-      if (before < max_pred) {
-        row_pos[b * max_pred + before] = static_cast<int32_t>(row + j);
-        row_label[b * max_pred + before] = static_cast<int32_t>(label);
+      if constexpr (WHOLE_WORD) {
+        if (before < max_pred) {
+          row_pos[b * max_pred + before] = static_cast<int32_t>(row + j);
+          row_label[b * max_pred + before] = static_cast<int32_t>(label);
+        }
+      } else {
+        const int slot = base + before;  // < base + n <= B * max_pred
+        positions[slot] = row + j;
+        gathered[slot] = label;
       }
     }
     out_ids[row + j] = id;
@@ -362,60 +320,45 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_select_kernel(
     out_am[row + j] = j <= last ? 1 : 0;
     if (dense != nullptr) dense[row + j] = label;
   }
-  if (tid == 0) {
-    int total = 0;
+
+  if constexpr (WHOLE_WORD) {
+    if (tid == 0) {
+      int total = 0;
 #pragma unroll
-    for (int w = 0; w < kMaskWords; ++w) total += __popcll(sel_bits[w]);
-    row_count[b] = total;
+      for (int w = 0; w < kMaskWords; ++w) total += __popcll(sel_bits[w]);
+      row_count[b] = total;
+    }
+  } else {
+    if (b == B - 1) fill_unused_slots(positions, gathered, base + n, B * max_pred);
   }
 }
 
-// Row b's first slot is the sum of the counts of the rows before it (strided
-// over the block, wave shuffle + LDS sum); its compact list moves there, and
-// the last block fills the slots no row used.
-__global__ __launch_bounds__(kMaskThreads) void mlm_mask_wwm_scatter_kernel(
+// Whole words, second launch: row b's first slot is the sum of the counts of
+// the rows before it; its compact list moves there, and the last block fills
+// the slots no row used.
+__global__ __launch_bounds__(kMaskThreads) void mlm_mask_scatter_kernel(
     const int32_t* __restrict__ row_count, const int32_t* __restrict__ row_pos,
     const int32_t* __restrict__ row_label, int64_t* __restrict__ positions,
     int64_t* __restrict__ gathered, int B, int max_pred) {
-  __shared__ int wave_sums[kMaskThreads / WAVE_SIZE];
   const int b = blockIdx.x;
-  const int tid = threadIdx.x;
-
-  int part = 0;
-  for (int r = tid; r < b; r += kMaskThreads)
-    part += min(max(row_count[r], 0), max_pred);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, WAVE_SIZE);
-  if ((tid & (WAVE_SIZE - 1)) == 0) wave_sums[tid / WAVE_SIZE] = part;
-  __syncthreads();
-  int base = 0;
-#pragma unroll
-  for (int w = 0; w < kMaskThreads / WAVE_SIZE; ++w) base += wave_sums[w];
-
-  const int count = min(max(row_count[b], 0), max_pred);
-  for (int i = tid; i < count; i += kMaskThreads) {
+  auto count_of = [&](int r) { return min(max(row_count[r], 0), max_pred); };
+  const int base = block_sum_before(b, count_of);
+  const int count = count_of(b);
+  for (int i = threadIdx.x; i < count; i += kMaskThreads) {
     positions[base + i] = row_pos[b * max_pred + i];  // base + i < B * max_pred
     gathered[base + i] = row_label[b * max_pred + i];
   }
-  if (b == B - 1) {
-    const int cap = B * max_pred;
-    for (int s = base + count + tid; s < cap; s += kMaskThreads) {
-      positions[s] = 0;
-      gathered[s] = -1;
-    }
-  }
+  if (b == B - 1)
+    fill_unused_slots(positions, gathered, base + count, B * max_pred);
 }
 
-}  // namespace
-
-namespace {
-
-// The argument checks both entry points share, and their outputs:
-// {masked_ids, token_type_ids, attention_mask, positions, gathered_labels
-// (, dense labels)}.
-std::vector<torch::Tensor> checked_mask_outputs(
+// Checks the arguments, allocates {masked_ids, token_type_ids,
+// attention_mask, positions, gathered_labels (, dense labels)} and launches:
+// whole words when `word_continues` is given, token-level otherwise.
+std::vector<torch::Tensor> mlm_mask_launch(
     const torch::Tensor& input_ids, const torch::Tensor& special,
     const torch::Tensor& sample_index, const torch::Tensor& count_table,
+    const torch::Tensor* word_continues, int64_t seed, int64_t epoch,
     int64_t max_pred, int64_t vocab_size, int64_t mask_token, int64_t t_keep,
     int64_t t_rand, bool dense_labels) {
   TORCH_CHECK(input_ids.is_cuda() && input_ids.dim() == 2 &&
@@ -460,6 +403,16 @@ std::vector<torch::Tensor> checked_mask_outputs(
               "mlm_mask: thresholds ", t_keep, " + ", t_rand,
               " must lie in [0, 2^32]");
   TORCH_CHECK(B * S < (int64_t{1} << 31), "mlm_mask: batch too large");
+  if (word_continues != nullptr) {
+    TORCH_CHECK(word_continues->device() == input_ids.device() &&
+                    word_continues->scalar_type() == torch::kUInt8 &&
+                    word_continues->dim() == 1 &&
+                    word_continues->size(0) == vocab_size &&
+                    word_continues->is_contiguous(),
+                "mlm_mask: word_continues must be contiguous uint8 [",
+                vocab_size, "] on the device of input_ids, got ",
+                word_continues->scalar_type(), " ", word_continues->sizes());
+  }
 
   auto opts = input_ids.options().dtype(torch::kInt64);
   std::vector<torch::Tensor> out = {
@@ -467,6 +420,47 @@ std::vector<torch::Tensor> checked_mask_outputs(
       torch::empty({B, S}, opts), torch::empty({B * max_pred}, opts),
       torch::empty({B * max_pred}, opts)};
   if (dense_labels) out.push_back(torch::empty({B, S}, opts));
+  if (B == 0) return out;
+
+  // whole words, per row: its count, then max_pred positions and max_pred
+  // labels
+  torch::Tensor scratch;
+  int32_t *row_count = nullptr, *row_pos = nullptr, *row_label = nullptr;
+  if (word_continues != nullptr) {
+    scratch = torch::empty({B * (2 * max_pred + 1)},
+                           input_ids.options().dtype(torch::kInt32));
+    row_count = scratch.data_ptr<int32_t>();
+    row_pos = row_count + B;
+    row_label = row_pos + B * max_pred;
+  }
+
+  auto stream = at::hip::getCurrentHIPStream();
+  const dim3 grid(static_cast<uint32_t>(B)), block(kMaskThreads);
+  const auto row_kernel = word_continues != nullptr
+                              ? mlm_mask_row_kernel<true>
+                              : mlm_mask_row_kernel<false>;
+  hipLaunchKernelGGL(
+      row_kernel, grid, block, 0, stream, input_ids.data_ptr<int32_t>(),
+      special.data_ptr<int32_t>(), sample_index.data_ptr<int64_t>(),
+      count_table.data_ptr<int32_t>(),
+      word_continues != nullptr ? word_continues->data_ptr<uint8_t>() : nullptr,
+      out[0].data_ptr<int64_t>(), out[1].data_ptr<int64_t>(),
+      out[2].data_ptr<int64_t>(),
+      dense_labels ? out[5].data_ptr<int64_t>() : nullptr,
+      out[3].data_ptr<int64_t>(), out[4].data_ptr<int64_t>(), row_count,
+      row_pos, row_label, static_cast<int>(B), static_cast<int>(S),
+      static_cast<int>(max_pred), static_cast<uint64_t>(seed),
+      static_cast<uint32_t>(epoch), static_cast<uint32_t>(vocab_size),
+      mask_token, static_cast<uint64_t>(t_keep),
+      static_cast<uint64_t>(t_keep + t_rand));
+  HIP_CHECK(hipGetLastError());
+  if (word_continues != nullptr) {
+    hipLaunchKernelGGL(mlm_mask_scatter_kernel, grid, block, 0, stream,
+                       row_count, row_pos, row_label,
+                       out[3].data_ptr<int64_t>(), out[4].data_ptr<int64_t>(),
+                       static_cast<int>(B), static_cast<int>(max_pred));
+    HIP_CHECK(hipGetLastError());
+  }
   return out;
 }
 
@@ -480,27 +474,9 @@ std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
                                     int64_t vocab_size, int64_t mask_token,
                                     int64_t t_keep, int64_t t_rand,
                                     bool dense_labels) {
-  auto out = checked_mask_outputs(input_ids, special, sample_index,
-                                  count_table, max_pred, vocab_size,
-                                  mask_token, t_keep, t_rand, dense_labels);
-  const int64_t B = input_ids.size(0), S = input_ids.size(1);
-  if (B == 0) return out;
-
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(
-      mlm_mask_kernel, dim3(static_cast<uint32_t>(B)), dim3(kMaskThreads), 0,
-      stream, input_ids.data_ptr<int32_t>(), special.data_ptr<int32_t>(),
-      sample_index.data_ptr<int64_t>(), count_table.data_ptr<int32_t>(),
-      out[0].data_ptr<int64_t>(), out[1].data_ptr<int64_t>(),
-      out[2].data_ptr<int64_t>(), out[3].data_ptr<int64_t>(),
-      out[4].data_ptr<int64_t>(),
-      dense_labels ? out[5].data_ptr<int64_t>() : nullptr, static_cast<int>(B),
-      static_cast<int>(S), static_cast<int>(max_pred),
-      static_cast<uint64_t>(seed), static_cast<uint32_t>(epoch),
-      static_cast<uint32_t>(vocab_size - 1), mask_token,
-      static_cast<uint64_t>(t_keep), static_cast<uint64_t>(t_keep + t_rand));
-  HIP_CHECK(hipGetLastError());
-  return out;
+  return mlm_mask_launch(input_ids, special, sample_index, count_table, nullptr,
+                         seed, epoch, max_pred, vocab_size, mask_token, t_keep,
+                         t_rand, dense_labels);
 }
 
 std::vector<torch::Tensor> mlm_mask_whole_word(
@@ -508,48 +484,9 @@ std::vector<torch::Tensor> mlm_mask_whole_word(
     torch::Tensor count_table, torch::Tensor word_continues, int64_t seed,
     int64_t epoch, int64_t max_pred, int64_t vocab_size, int64_t mask_token,
     int64_t t_keep, int64_t t_rand, bool dense_labels) {
-  auto out = checked_mask_outputs(input_ids, special, sample_index,
-                                  count_table, max_pred, vocab_size,
-                                  mask_token, t_keep, t_rand, dense_labels);
-  TORCH_CHECK(word_continues.device() == input_ids.device() &&
-                  word_continues.scalar_type() == torch::kUInt8 &&
-                  word_continues.dim() == 1 &&
-                  word_continues.size(0) == vocab_size &&
-                  word_continues.is_contiguous(),
-              "mlm_mask: word_continues must be contiguous uint8 [",
-              vocab_size, "] on the device of input_ids, got ",
-              word_continues.scalar_type(), " ", word_continues.sizes());
-  const int64_t B = input_ids.size(0), S = input_ids.size(1);
-  if (B == 0) return out;
-
-  // per row: its count, then max_pred positions and max_pred labels
-  auto scratch = torch::empty({B * (2 * max_pred + 1)},
-                              input_ids.options().dtype(torch::kInt32));
-  int32_t* row_count = scratch.data_ptr<int32_t>();
-  int32_t* row_pos = row_count + B;
-  int32_t* row_label = row_pos + B * max_pred;
-
-  auto stream = at::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(
-      mlm_mask_wwm_select_kernel, dim3(static_cast<uint32_t>(B)),
-      dim3(kMaskThreads), 0, stream, input_ids.data_ptr<int32_t>(),
-      special.data_ptr<int32_t>(), sample_index.data_ptr<int64_t>(),
-      count_table.data_ptr<int32_t>(), word_continues.data_ptr<uint8_t>(),
-      out[0].data_ptr<int64_t>(), out[1].data_ptr<int64_t>(),
-      out[2].data_ptr<int64_t>(),
-      dense_labels ? out[5].data_ptr<int64_t>() : nullptr, row_count, row_pos,
-      row_label, static_cast<int>(S), static_cast<int>(max_pred),
-      static_cast<uint64_t>(seed), static_cast<uint32_t>(epoch),
-      static_cast<uint32_t>(vocab_size), mask_token,
-      static_cast<uint64_t>(t_keep), static_cast<uint64_t>(t_keep + t_rand));
-  HIP_CHECK(hipGetLastError());
-  hipLaunchKernelGGL(mlm_mask_wwm_scatter_kernel,
-                     dim3(static_cast<uint32_t>(B)), dim3(kMaskThreads), 0,
-                     stream, row_count, row_pos, row_label,
-                     out[3].data_ptr<int64_t>(), out[4].data_ptr<int64_t>(),
-                     static_cast<int>(B), static_cast<int>(max_pred));
-  HIP_CHECK(hipGetLastError());
-  return out;
+  return mlm_mask_launch(input_ids, special, sample_index, count_table,
+                         &word_continues, seed, epoch, max_pred, vocab_size,
+                         mask_token, t_keep, t_rand, dense_labels);
 }
 
 }  // namespace bpa

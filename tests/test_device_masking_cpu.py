@@ -2,7 +2,6 @@
 mask invariants on synthetic shards, independence from how the run is
 launched, the distribution of the draws on fixed inputs, and the runner."""
 
-import csv
 import json
 import math
 
@@ -20,10 +19,22 @@ from bert_pytorch_amd.data import (
     synth,
 )
 from bert_pytorch_amd.parallel import comm
-from test_gpu_mlm_mask import VECTORS, _vector_inputs, spec_mlm_mask
+from mlm_mask_spec import (
+    MASK,
+    TOKEN_CASES,
+    VECTORS,
+    VOCAB,
+    _argv,
+    _losses,
+    _raw,
+    assert_equal_spec,
+    make_workspace,
+    run_op,
+    spec_mlm_mask,
+    spec_of,
+    vector_inputs,
+)
 
-VOCAB = 30522
-MASK = 103
 SEQ = 48
 MAX_PRED = 8
 PROB = 0.15
@@ -74,15 +85,6 @@ def nsp_shards(tmp_path_factory):
         str(directory), num_shards=2, samples_per_shard=16, seq_len=SEQ,
         vocab_size=VOCAB, seed=5,
     )
-
-
-def _raw(files):
-    ids, special = [], []
-    for path in files:
-        with h5lite.H5LiteFile(path) as f:
-            ids.append(np.asarray(f["input_ids"]))
-            special.append(np.asarray(f["special_token_positions"]))
-    return np.concatenate(ids), np.concatenate(special)
 
 
 def _mask_all(batch, epoch, masker=None, dense=True):
@@ -202,9 +204,15 @@ def test_fallback_equals_numpy_spec(shards):
         assert torch.equal(g, torch.from_numpy(w))
 
 
+@pytest.mark.parametrize("name", list(TOKEN_CASES))
+def test_cpu_op_equals_numpy_spec(name):
+    case, want = spec_of(name, False)
+    assert_equal_spec(run_op(**case), want)
+
+
 @pytest.mark.parametrize("vec", VECTORS, ids=["vector1", "vector2"])
 def test_fallback_on_the_cross_check_vectors(vec):
-    ids, special = _vector_inputs()
+    ids, special = vector_inputs()
     t_keep, t_rand = ops.mlm_thresholds(0.1, 0.1)
     masked, _tt, am, positions, gathered, labels = ops.mlm_mask(
         torch.from_numpy(ids), torch.from_numpy(special),
@@ -352,40 +360,7 @@ def test_distribution_on_fixed_inputs():
 # ---------------------------------------------------------------------------
 @pytest.fixture
 def workspace(tmp_path):
-    data_dir = tmp_path / "data"
-    synth.make_dataset(
-        str(data_dir), num_shards=2, samples_per_shard=16, seq_len=32,
-        vocab_size=512, seed=0,
-    )
-    model_cfg = {
-        "vocab_size": 512, "hidden_size": 64, "num_hidden_layers": 2,
-        "num_attention_heads": 4, "intermediate_size": 128,
-        "max_position_embeddings": 64, "type_vocab_size": 2,
-        "hidden_act": "gelu", "hidden_dropout_prob": 0.1,
-        "attention_probs_dropout_prob": 0.1, "initializer_range": 0.02,
-        "next_sentence": True,
-    }
-    cfg_path = tmp_path / "model.json"
-    cfg_path.write_text(json.dumps(model_cfg))
-    return tmp_path, str(data_dir), str(cfg_path)
-
-
-def _argv(tmp_path, data_dir, cfg_path, *extra):
-    return [
-        "--model_config_file", cfg_path, "--input_dir", data_dir,
-        "--output_dir", str(tmp_path / "out"), "--local_batch_size", "4",
-        "--global_batch_size", "8", "--max_steps", "2",
-        "--learning_rate", "1e-3", "--warmup_proportion", "0.2",
-        "--num_steps_per_checkpoint", "2", "--seed", "7",
-        "--num_workers", "0", "--max_predictions_per_seq", "5", *extra,
-    ]
-
-
-def _losses(tmp_path):
-    (path,) = (tmp_path / "out").glob("*_metrics.csv")
-    with open(path, newline="", encoding="utf-8") as f:
-        return [float(r["step_loss"]) for r in csv.DictReader(f)
-                if r["tag"] == "train"]
+    return make_workspace(tmp_path, with_vocab=False)
 
 
 @pytest.mark.parametrize("extra", [(), ("--unpad",)], ids=["padded", "unpad"])

@@ -1,9 +1,10 @@
-"""Whole-word masking on the device (the two whole-word kernels of
-csrc/ops/mlm_mask.hip, ``ops.mlm_mask(..., word_continues=)``).
+"""Whole-word masking on the device (the whole-word instantiation of the row
+kernel and the scatter kernel of csrc/ops/mlm_mask.hip,
+``ops.mlm_mask(..., word_continues=)``).
 
 The expected values come from ``spec_mlm_mask_wwm``, the sequential
-plain-Python specification in tests/test_whole_word_masking_cpu.py; the
-cases are that file's too, each computed once per session. Integer
+plain-Python specification in tests/mlm_mask_spec.py; the cases are that
+file's too, each computed once per session. Integer
 arithmetic end to end: every comparison is ``torch.equal``. All tests
 @pytest.mark.gpu.
 """
@@ -12,11 +13,11 @@ import numpy as np
 import pytest
 import torch
 
-from test_whole_word_masking_cpu import (
-    CASES,
+from mlm_mask_spec import (
     MASK,
     NAMES,
     VOCAB,
+    WWM_CASES as CASES,
     assert_equal_spec,
     check_case_facts,
     run_op,
@@ -35,7 +36,7 @@ DEV = "cuda:0"
 @pytest.mark.parametrize("dense", [True, False], ids=["dense", "no_dense"])
 @pytest.mark.parametrize("name", list(CASES))
 def test_kernel_equals_spec(name, dense):
-    case, want = spec_of(name)
+    case, want = spec_of(name, True)
     check_case_facts(name, case, want)
     got = run_op(**case, dense_labels=dense, device=DEV)
     assert all(t.is_cuda for t in got[:5])
@@ -45,7 +46,7 @@ def test_kernel_equals_spec(name, dense):
 @pytest.mark.parametrize("name", ["B8_S512", "B300_S16_prefix",
                                   "vocab_edge_ids"])
 def test_kernel_equals_fallback(name):
-    case, _ = spec_of(name)
+    case, _ = spec_of(name, True)
     got = run_op(**case, device=DEV)
     fallback = run_op(**case, device="cpu")
     for n, g, f in zip(NAMES, got, fallback):
@@ -53,7 +54,7 @@ def test_kernel_equals_fallback(name):
 
 
 def test_two_epochs_give_different_masks():
-    case, want = spec_of("B8_S128")
+    case, want = spec_of("B8_S128", True)
     other = dict(case, epoch=case["epoch"] + 1)
     got = run_op(**other, device=DEV)
     assert not torch.equal(got[5].cpu(), torch.from_numpy(want[5]))
@@ -62,7 +63,7 @@ def test_two_epochs_give_different_masks():
 
 
 def test_a_sample_has_one_mask_in_any_batch():
-    case, want = spec_of("B8_S128")
+    case, want = spec_of("B8_S128", True)
     index = np.asarray(case["sample_index"])
     for pick in ([5, 2], [0, 7, 7, 3, 5]):
         sub = dict(case, input_ids=case["input_ids"][pick],
@@ -77,7 +78,7 @@ def test_a_sample_has_one_mask_in_any_batch():
 @pytest.mark.parametrize("name", ["B8_S128", "B300_S16_prefix", "B3_S1024",
                                   "max_pred_below_table"])
 def test_all_zero_table_equals_the_token_level_kernel(name):
-    case, _ = spec_of(name)
+    case, _ = spec_of(name, True)
     zeros = dict(case, word_continues=np.zeros(VOCAB, dtype=np.uint8))
     got = run_op(**zeros, device=DEV)
     plain = run_op(**dict(case, word_continues=None), device=DEV)
@@ -87,7 +88,7 @@ def test_all_zero_table_equals_the_token_level_kernel(name):
 
 def test_no_host_sync():
     """The op reads nothing back: it runs with sync debugging set to raise."""
-    case, want = spec_of("B8_S128")
+    case, want = spec_of("B8_S128", True)
     S = case["input_ids"].shape[1]
     ids = torch.from_numpy(case["input_ids"]).to(DEV)
     special = torch.from_numpy(case["special"]).to(DEV)
