@@ -18,7 +18,14 @@ table reports the median over rounds with the min-max spread.
           and the scatter kernel, two launches, on the same rows, with a
           table that marks a fifth of the vocabulary as continuation pieces
 
-``--trace mask|gather|wwm`` instead issues ``--calls`` calls of one contender
+``--span`` times all three selection rules, alternating:
+  mask, wwm as above, and
+  span    ops.mlm_mask(..., word_continues=table, span_table=): the span
+          instantiation of the row kernel and the scatter kernel, two
+          launches, same rows and word table, spans of up to SPAN_MAX words
+          with geometric parameter SPAN_P (SpanBERT's 10 and 0.2)
+
+``--trace mask|gather|wwm|span`` instead issues ``--calls`` calls of one contender
 per shape after a warm-up and nothing else, for a kernel trace:
     rocprofv3 --kernel-trace --stats -d OUT -- \
         python benchmarks/mlm_mask_bench.py --trace mask
@@ -47,6 +54,7 @@ ROUNDS, ITERS, WARMUP = 15, 50, 10
 VOCAB, MASK_TOKEN, PROB = 30522, 103, 0.15
 SHAPES = [(96, 128, 20), (16, 512, 76)]
 CONTINUES = 0.2  # --whole_word: share of the vocabulary that continues a word
+SPAN_P, SPAN_MAX = 0.2, 10
 
 
 def make_rows(bsz, seq, seed):
@@ -84,19 +92,20 @@ def padded_gather(masked_lm_labels, max_predictions_per_seq):
     return positions[:cap], gathered_labels[:cap]
 
 
-def contenders(bsz, seq, max_pred, whole_word=False):
+def contenders(bsz, seq, max_pred, whole_word=False, span=False):
     ids, special, index = make_rows(bsz, seq, seed=bsz + seq)
     table = ops.mlm_count_table(seq, PROB, max_pred).to(DEV)
     t_keep, t_rand = ops.mlm_thresholds(0.1, 0.1)
 
-    def run_mask(dense=False, word_continues=None):
+    def run_mask(dense=False, word_continues=None, span_table=None):
         return ops.mlm_mask(
             ids, special, index, table, seed=42, epoch=0, max_pred=max_pred,
             vocab_size=VOCAB, mask_token=MASK_TOKEN, t_keep=t_keep,
             t_rand=t_rand, dense_labels=dense, word_continues=word_continues,
+            span_table=span_table,
         )
 
-    if whole_word:
+    if whole_word or span:
         # a fifth of the (uniformly drawn) ids continue a word: words of
         # 1.25 pieces on average, as WordPiece gives on English text
         rng = np.random.default_rng(bsz * seq)
@@ -115,7 +124,23 @@ def contenders(bsz, seq, max_pred, whole_word=False):
         got = run_mask(dense=True, word_continues=words)
         positions, gathered = padded_gather(got[5], max_pred)
         assert torch.equal(positions, got[3]) and torch.equal(gathered, got[4])
-        return {"mask": run_mask, "wwm": run_wwm}
+        if not span:
+            return {"mask": run_mask, "wwm": run_wwm}
+
+        lengths = ops.mlm_span_table(SPAN_P, SPAN_MAX).to(DEV)
+        one = ops.mlm_span_table(SPAN_P, 1).to(DEV)
+
+        def run_span():
+            return run_mask(word_continues=words, span_table=lengths)
+
+        # spans of one word select what whole-word masking selects
+        alone = run_mask(dense=True, word_continues=words, span_table=one)
+        for k in (1, 2, 3, 4, 5):
+            assert torch.equal(alone[k], got[k])
+        got = run_mask(dense=True, word_continues=words, span_table=lengths)
+        positions, gathered = padded_gather(got[5], max_pred)
+        assert torch.equal(positions, got[3]) and torch.equal(gathered, got[4])
+        return {"mask": run_mask, "wwm": run_wwm, "span": run_span}
 
     out = run_mask(dense=True)
     labels = out[5]
@@ -142,7 +167,8 @@ def time_once(fn):
 
 def trace(which, calls):
     for bsz, seq, max_pred in SHAPES:
-        fn = contenders(bsz, seq, max_pred, whole_word=which == "wwm")[which]
+        fn = contenders(bsz, seq, max_pred, whole_word=which == "wwm",
+                        span=which == "span")[which]
         for _ in range(WARMUP):
             fn()
         torch.cuda.synchronize()
@@ -156,32 +182,38 @@ def trace(which, calls):
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--out", default=None, help="also write the table here")
-    parser.add_argument("--trace", choices=["mask", "gather", "wwm"],
+    parser.add_argument("--trace", choices=["mask", "gather", "wwm", "span"],
                         default=None)
     parser.add_argument("--calls", type=int, default=200)
     parser.add_argument("--whole_word", action="store_true",
                         help="time whole-word masking (word_continues=, two "
                              "launches) against token-level ops.mlm_mask")
+    parser.add_argument("--span", action="store_true",
+                        help="time token-level, whole-word and span masking "
+                             "(span_table=), alternating")
     args = parser.parse_args()
     assert torch.cuda.is_available(), "this benchmark needs a GPU"
     if args.trace:
         trace(args.trace, args.calls)
         return
 
-    second = (
-        "ops.mlm_mask, whole words" if args.whole_word
-        else "padded gather (torch)"
-    )
+    if args.span:
+        others = ["ops.mlm_mask, whole words", "ops.mlm_mask, spans"]
+    elif args.whole_word:
+        others = ["ops.mlm_mask, whole words"]
+    else:
+        others = ["padded gather (torch)"]
     lines = [
         f"device: {torch.cuda.get_device_name(0)}; {ROUNDS} alternating rounds "
         f"x {ITERS} back-to-back calls, median us per call (min-max over "
         "rounds), host launch cost included",
         "",
-        f"| B | S | max_pred | ops.mlm_mask | {second} |",
-        "|---|---|---|---|---|",
+        "| B | S | max_pred | ops.mlm_mask | " + " | ".join(others) + " |",
+        "|---|---|---|---|" + "---|" * len(others),
     ]
     for bsz, seq, max_pred in SHAPES:
-        fns = list(contenders(bsz, seq, max_pred, args.whole_word).values())
+        fns = list(contenders(bsz, seq, max_pred, args.whole_word,
+                              args.span).values())
         for fn in fns:
             for _ in range(WARMUP):
                 fn()
@@ -195,7 +227,8 @@ def main():
             return f"{statistics.median(t):.1f} ({min(t):.1f}-{max(t):.1f})"
 
         lines.append(
-            f"| {bsz} | {seq} | {max_pred} | {cell(times[0])} | {cell(times[1])} |"
+            f"| {bsz} | {seq} | {max_pred} | "
+            + " | ".join(cell(t) for t in times) + " |"
         )
     text = "\n".join(lines)
     print(text)

@@ -17,7 +17,10 @@ Re-designed from the reference's ``ShardedPretrainingDataset``
   and its global index for ``DeviceMasker`` (masking.py);
   ``whole_word_masking`` makes the dynamic masks of whole words (the word
   rule and greedy fill of ``ops.mlm_mask``, drawn from this dataset's
-  generator); static masks stay token-level;
+  generator); ``span_masking`` makes them of spans of whole words (the
+  span fill of ``ops.mlm_mask(..., span_table=)``, lengths and order from
+  this dataset's generator, one keep / random / mask decision per span);
+  static masks stay token-level;
 * a rank-chunked sequential sampler whose position checkpoints into the
   training state dict.
 
@@ -59,15 +62,35 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         device_masking: bool = False,
         whole_word_masking: bool = False,
         word_continues=None,
+        span_masking: bool = False,
+        span_max_length: int = 10,
+        span_geometric_p: float = 0.2,
     ):
         if original_token_prob + random_token_prob > 1:
             raise ValueError("original_token_prob + random_token_prob > 1")
-        if whole_word_masking and not (device_masking or static_masking):
+        # static (evaluation) masks stay token-level and device_masking
+        # masks nothing here: words and spans are a matter of the dynamic path
+        span_masking = span_masking and not (device_masking or static_masking)
+        whole_word_masking = (
+            whole_word_masking and not (device_masking or static_masking)
+        ) or span_masking
+        if span_masking:
+            if not 0 < span_geometric_p <= 1:
+                raise ValueError(
+                    f"span_geometric_p must be in (0, 1], got "
+                    f"{span_geometric_p}"
+                )
+            if not 1 <= span_max_length <= 32:
+                raise ValueError(
+                    f"span_max_length must be in [1, 32], got "
+                    f"{span_max_length}"
+                )
+        if whole_word_masking:
             if word_continues is None:
                 raise ValueError(
-                    "whole_word_masking needs word_continues, the uint8 "
-                    "[vocab_size] table of tokenization."
-                    "word_continuation_table"
+                    f"{'span' if span_masking else 'whole_word'}_masking "
+                    "needs word_continues, the uint8 [vocab_size] table of "
+                    "tokenization.word_continuation_table"
                 )
             word_continues = np.asarray(word_continues, dtype=np.uint8)
             if word_continues.shape != (vocab_size,):
@@ -99,11 +122,14 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         self.seed = seed
         self.static_masking = static_masking
         self.device_masking = device_masking
-        # static (evaluation) masks stay token-level and device_masking
-        # masks nothing here: whole words are a matter of the dynamic path
-        self.whole_word_masking = (
-            whole_word_masking and not (device_masking or static_masking)
+        self.whole_word_masking = whole_word_masking  # span masking included
+        self.span_masking = span_masking
+        self.span_max_length = span_max_length
+        # P(L = k) of the clipped geometric law, k = 1..span_max_length
+        law = span_geometric_p * (1 - span_geometric_p) ** np.arange(
+            span_max_length if span_masking else 1
         )
+        self._span_law = law / law.sum()
         self.word_continues = word_continues if self.whole_word_masking else None
         self.epoch = 0
         self._rng = np.random.default_rng(seed)
@@ -182,9 +208,14 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
             if self.whole_word_masking:
                 raise ValueError(
                     f"{self.files[self.file_idx]} is a pre-masked shard (it "
-                    "has no special_token_positions): whole_word_masking / "
-                    "--whole_word_masking needs unmasked shards; drop the "
-                    "flag to train on this one"
+                    "has no special_token_positions): "
+                    + (
+                        "span_masking / --span_masking"
+                        if self.span_masking
+                        else "whole_word_masking / --whole_word_masking"
+                    )
+                    + " needs unmasked shards; drop the flag to train on "
+                    "this one"
                 )
             segment_ids = self.data["segment_ids"][local]
             input_mask = self.data["input_mask"][local]
@@ -276,6 +307,11 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
             self.max_pred_per_seq,
             max(1, int(candidates.size * self.masked_lm_prob)),
         )
+        if self.span_masking:
+            spans = self._span_indices(input_ids, candidates, mask_count, rng)
+            return self._substitute_spans(
+                input_ids, masked_lm_labels, spans, rng
+            )
         if self.whole_word_masking:
             mask_indices = self._whole_word_indices(
                 input_ids, candidates, mask_count, rng
@@ -294,6 +330,25 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
                 input_ids[idx] = self.mask_token_index
         return input_ids, masked_lm_labels
 
+    def _words(
+        self, input_ids: np.ndarray, candidates: np.ndarray
+    ) -> List[List[int]]:
+        """The words of a row, in position order: a candidate starts a word
+        unless its id continues one and the position before it is a
+        candidate."""
+        words: List[List[int]] = []
+        for j in candidates.tolist():
+            token = int(input_ids[j])
+            continues = (
+                0 <= token < self.word_continues.size
+                and self.word_continues[token] == 1
+            )
+            if continues and words and words[-1][-1] == j - 1:
+                words[-1].append(j)
+            else:
+                words.append([j])
+        return words
+
     def _whole_word_indices(
         self,
         input_ids: np.ndarray,
@@ -306,17 +361,7 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
         continues one and the position before it is a candidate; the words
         are visited in a random order and one is taken, all of it, when it
         still fits into ``mask_count``, until ``mask_count`` is reached."""
-        words: List[List[int]] = []
-        for j in candidates.tolist():
-            token = int(input_ids[j])
-            continues = (
-                0 <= token < self.word_continues.size
-                and self.word_continues[token] == 1
-            )
-            if continues and words and words[-1][-1] == j - 1:
-                words[-1].append(j)
-            else:
-                words.append([j])
+        words = self._words(input_ids, candidates)
         chosen: List[int] = []
         for w in rng.permutation(len(words)):
             if len(chosen) >= mask_count:
@@ -325,6 +370,73 @@ class ShardedPretrainingDataset(torch.utils.data.Dataset):
                 continue
             chosen.extend(words[w])
         return np.array(chosen, dtype=np.int64)
+
+    def _span_indices(
+        self,
+        input_ids: np.ndarray,
+        candidates: np.ndarray,
+        mask_count: int,
+        rng: np.random.Generator,
+    ) -> List[List[int]]:
+        """Span selection, the rule of ``ops.mlm_mask(..., span_table=)``
+        with this dataset's generator: the words are visited in a random
+        order; a free word that still fits into ``mask_count`` anchors a
+        span, which grows over the words that follow it directly (a special
+        token ends it) up to a length of the clipped geometric law, while
+        they are free and fit. The spans, each a list of positions."""
+        words = self._words(input_ids, candidates)
+        visit = rng.permutation(len(words))  # drawn first, as for whole words
+        lengths = 1 + rng.choice(
+            self.span_max_length, size=len(words), p=self._span_law
+        )
+        taken = [False] * len(words)
+        spans: List[List[int]] = []
+        m = 0
+        for w in visit:
+            if m >= mask_count:
+                break
+            if taken[w] or m + len(words[w]) > mask_count:
+                continue
+            span = list(words[w])
+            taken[w] = True
+            x = w
+            for _ in range(int(lengths[w]) - 1):
+                y = x + 1
+                if (
+                    y == len(words)
+                    or words[y][0] != words[x][-1] + 1
+                    or taken[y]
+                    or m + len(span) + len(words[y]) > mask_count
+                ):
+                    break
+                span.extend(words[y])
+                taken[y] = True
+                x = y
+            m += len(span)
+            spans.append(span)
+        return spans
+
+    def _substitute_spans(
+        self,
+        input_ids: np.ndarray,
+        masked_lm_labels: np.ndarray,
+        spans: List[List[int]],
+        rng: np.random.Generator,
+    ) -> Tuple[np.ndarray, np.ndarray]:
+        """One keep / random / mask decision per span; a random span draws
+        a token per position."""
+        draws = rng.random(len(spans))
+        for span, draw in zip(spans, draws):
+            masked_lm_labels[span] = input_ids[span]
+            if draw < self.original_token_prob:
+                continue  # keep the original tokens
+            if draw < self.original_token_prob + self.random_token_prob:
+                input_ids[span] = rng.integers(
+                    0, self.vocab_size - 1, size=len(span)
+                )
+            else:
+                input_ids[span] = self.mask_token_index
+        return input_ids, masked_lm_labels
 
     @staticmethod
     def _premasked_labels(

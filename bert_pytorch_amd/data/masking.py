@@ -28,10 +28,14 @@ class DeviceMasker:
         original_token_prob: float = 0.1,
         random_token_prob: float = 0.1,
         word_continues: Optional[torch.Tensor] = None,
+        span_max_length: Optional[int] = None,
+        span_geometric_p: float = 0.2,
     ):
         """``word_continues`` (uint8 [vocab_size],
         ``tokenization.word_continuation_table``) turns on whole-word
-        masking."""
+        masking; ``span_max_length`` on top of it turns on span masking
+        (spans of whole words, ``ops.mlm_span_table(span_geometric_p,
+        span_max_length)``)."""
         self.seed = int(seed)
         self.mask_token_index = int(mask_token_index)
         self.max_pred_per_seq = int(max_pred_per_seq)
@@ -53,6 +57,17 @@ class DeviceMasker:
                 )
         self.word_continues = word_continues
         self._word_tables: Dict[torch.device, torch.Tensor] = {}
+        self.span_table = None
+        if span_max_length is not None:
+            if word_continues is None:
+                raise ValueError(
+                    "span_max_length needs word_continues: spans are made "
+                    "of whole words"
+                )
+            self.span_table = ops.mlm_span_table(
+                span_geometric_p, span_max_length
+            )
+        self._span_tables: Dict[torch.device, torch.Tensor] = {}
 
     def word_table(self, device: torch.device) -> Optional[torch.Tensor]:
         """``word_continues`` on ``device``, uploaded once; None when
@@ -62,6 +77,17 @@ class DeviceMasker:
         if device not in self._word_tables:
             self._word_tables[device] = self.word_continues.to(device)
         return self._word_tables[device]
+
+    def span_length_table(
+        self, device: torch.device
+    ) -> Optional[torch.Tensor]:
+        """``ops.mlm_span_table`` on ``device``, uploaded once; None without
+        span masking."""
+        if self.span_table is None:
+            return None
+        if device not in self._span_tables:
+            self._span_tables[device] = self.span_table.to(device)
+        return self._span_tables[device]
 
     def count_table(self, seq_len: int, device: torch.device) -> torch.Tensor:
         """``ops.mlm_count_table`` for this sequence length, uploaded once."""
@@ -84,5 +110,6 @@ class DeviceMasker:
             vocab_size=self.vocab_size, mask_token=self.mask_token_index,
             t_keep=self.t_keep, t_rand=self.t_rand,
             word_continues=self.word_table(input_ids.device),
+            span_table=self.span_length_table(input_ids.device),
         )
         return masked, segment_ids, input_mask, positions, gathered, nsp_labels

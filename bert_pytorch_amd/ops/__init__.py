@@ -79,4 +79,9 @@ from .matmul import linear_nobias  # noqa: E402,F401
 from .ffn import ffn_supported, fused_ffn  # noqa: E402,F401
 from .mlm import MlmEval, mlm_decoder_eval, mlm_decoder_loss  # noqa: E402,F401
 from .kfac_factor import factor_update  # noqa: E402,F401
-from .mlm_mask import mlm_count_table, mlm_mask, mlm_thresholds  # noqa: E402,F401
+from .mlm_mask import (  # noqa: E402,F401
+    mlm_count_table,
+    mlm_mask,
+    mlm_span_table,
+    mlm_thresholds,
+)

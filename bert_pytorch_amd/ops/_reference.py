@@ -204,8 +204,8 @@ def philox4x32_10_words(c0, c1, c2, c3, k0: int, k1: int) -> list[torch.Tensor]:
 def _mlm_mask_draws(
     input_ids, special, sample_index, count_table, seed, epoch, max_pred
 ):
-    """What both mask functions share up to the selection: ``(ids,
-    token_type, attention_mask, cand, n, j, w0, w1, w2)``."""
+    """What the mask functions share up to the selection: ``(ids,
+    token_type, attention_mask, cand, n, j, w0, w1, w2, w3)``."""
     bsz, seq = input_ids.shape
     dev = input_ids.device
     ids = input_ids.long()
@@ -227,10 +227,10 @@ def _mlm_mask_draws(
     c3 = (((index >> 32) & 0x7FFFFFFF) | 0x80000000).expand(bsz, seq)
     c0 = j.expand(bsz, seq)
     c1 = torch.full_like(c0, epoch & _LO32)
-    w0, w1, w2, _ = philox4x32_10_words(
+    w0, w1, w2, w3 = philox4x32_10_words(
         c0, c1, c2, c3, seed & _LO32, seed >> 32
     )
-    return ids, token_type, attention_mask, cand, n, j, w0, w1, w2
+    return ids, token_type, attention_mask, cand, n, j, w0, w1, w2, w3
 
 
 def _mlm_mask_outputs(
@@ -284,8 +284,11 @@ def mlm_mask(
     sample_index [B], count_table [S+1] ->
     (masked_ids, token_type_ids, attention_mask, positions,
     gathered_labels, dense_labels), all int64."""
-    ids, token_type, attention_mask, cand, n, j, w0, w1, w2 = _mlm_mask_draws(
-        input_ids, special, sample_index, count_table, seed, epoch, max_pred
+    ids, token_type, attention_mask, cand, n, j, w0, w1, w2, _ = (
+        _mlm_mask_draws(
+            input_ids, special, sample_index, count_table, seed, epoch,
+            max_pred,
+        )
     )
     seq = ids.shape[1]
     # (w0 << 32 | j) orders like w0 * S + j; non-candidates sort last
@@ -315,27 +318,19 @@ def mlm_mask_whole_word(
     """``mlm_mask`` with whole-word masking (the two whole-word kernels of
     csrc/ops/mlm_mask.hip in torch integer arithmetic). word_continues
     uint8 [vocab_size] is 1 where a vocabulary entry continues a word."""
-    ids, token_type, attention_mask, cand, n, j, w0, w1, w2 = _mlm_mask_draws(
-        input_ids, special, sample_index, count_table, seed, epoch, max_pred
+    ids, token_type, attention_mask, cand, n, j, w0, w1, w2, _ = (
+        _mlm_mask_draws(
+            input_ids, special, sample_index, count_table, seed, epoch,
+            max_pred,
+        )
     )
-    bsz, seq = ids.shape
+    bsz = ids.shape[0]
     n = n.squeeze(1)
-
-    # words: a candidate starts one unless its id continues a candidate
-    in_vocab = (ids >= 0) & (ids < vocab_size)
-    continues = word_continues.long()[ids.clamp(0, vocab_size - 1)] == 1
-    prev_cand = torch.cat(
-        [torch.zeros_like(cand[:, :1]), cand[:, :-1]], dim=1
+    start, head, length, order = _mlm_mask_words(
+        ids, cand, j, w0, word_continues, vocab_size
     )
-    start = cand & ~(in_vocab & continues & prev_cand)
-    head = torch.cummax(
-        torch.where(start, j, torch.full_like(j, -1)), dim=1
-    ).values.clamp(min=0)  # of a candidate: the start of its word
-    length = torch.zeros_like(ids).scatter_add_(1, head, cand.long())
 
-    # ascending (w0 << 32 | first), then the greedy fill, a rank at a time
-    key = torch.where(start, w0 * seq + j, torch.full_like(w0, 1 << 62))
-    order = torch.argsort(key, dim=1)
+    # the greedy fill, a rank at a time
     length_by_rank = length.gather(1, order)
     start_by_rank = start.gather(1, order)
     taken = torch.zeros_like(start)
@@ -350,6 +345,111 @@ def mlm_mask_whole_word(
     selected = cand & word_selected.gather(1, head)
     return _mlm_mask_outputs(
         ids, token_type, attention_mask, selected, w1, w2, max_pred,
+        vocab_size, mask_token, t_keep, t_rand,
+    )
+
+
+def _mlm_mask_words(ids, cand, j, w0, word_continues, vocab_size):
+    """The words of every row: ``start`` [B,S] (a candidate that starts a
+    word), ``head`` [B,S] (of a candidate: the start of its word),
+    ``length`` [B,S] (at a start: the word's positions) and ``order`` [B,S]
+    (positions by ascending ``(w0 << 32) | first``, the starts first)."""
+    seq = ids.shape[1]
+    # a candidate starts a word unless its id continues a candidate
+    in_vocab = (ids >= 0) & (ids < vocab_size)
+    continues = word_continues.long()[ids.clamp(0, vocab_size - 1)] == 1
+    prev_cand = torch.cat(
+        [torch.zeros_like(cand[:, :1]), cand[:, :-1]], dim=1
+    )
+    start = cand & ~(in_vocab & continues & prev_cand)
+    head = torch.cummax(
+        torch.where(start, j, torch.full_like(j, -1)), dim=1
+    ).values.clamp(min=0)  # of a candidate: the start of its word
+    length = torch.zeros_like(ids).scatter_add_(1, head, cand.long())
+
+    key = torch.where(start, w0 * seq + j, torch.full_like(w0, 1 << 62))
+    return start, head, length, torch.argsort(key, dim=1)
+
+
+def mlm_mask_span(
+    input_ids: torch.Tensor,
+    special: torch.Tensor,
+    sample_index: torch.Tensor,
+    count_table: torch.Tensor,
+    word_continues: torch.Tensor,
+    span_table: torch.Tensor,
+    seed: int,
+    epoch: int,
+    max_pred: int,
+    vocab_size: int,
+    mask_token: int,
+    t_keep: int,
+    t_rand: int,
+) -> tuple[torch.Tensor, ...]:
+    """``mlm_mask`` with span masking (the span instantiation of
+    csrc/ops/mlm_mask.hip in torch integer arithmetic). span_table int64
+    [Lmax] is ``ops.mlm_span_table``: a word that is taken grows over the
+    words that follow it, and the span shares the anchor's decision."""
+    ids, token_type, attention_mask, cand, n, j, w0, w1, w2, w3 = (
+        _mlm_mask_draws(
+            input_ids, special, sample_index, count_table, seed, epoch,
+            max_pred,
+        )
+    )
+    bsz, seq = ids.shape
+    n = n.squeeze(1)
+    start, head, length, order = _mlm_mask_words(
+        ids, cand, j, w0, word_continues, vocab_size
+    )
+    lmax = span_table.numel()
+    # words of the span a start anchors, from its own w3
+    span_len = 1 + (
+        w3.unsqueeze(-1) >= span_table.long()[: lmax - 1]
+    ).sum(-1)
+
+    # anchor_of[b, first]: 1 + the anchor's position of the span that holds
+    # the word at `first`, 0 while the word is free
+    anchor_of = torch.zeros_like(ids)
+    zero = torch.zeros_like(n)
+    rows = torch.arange(bsz, device=ids.device)
+    m = torch.zeros_like(n)
+    for r in range(int(start.sum(1).max()) if bsz else 0):
+        anchor = order[:, r]
+        x_len = length[rows, anchor]
+        grow = (
+            start[rows, anchor] & (anchor_of[rows, anchor] == 0)
+            & (m < n) & (m + x_len <= n)
+        )
+        mark = anchor + 1
+        anchor_of[rows, anchor] = torch.where(
+            grow, mark, anchor_of[rows, anchor]
+        )
+        want = span_len[rows, anchor]
+        x, t = anchor, torch.where(grow, x_len, zero)
+        for step in range(1, lmax):
+            y = x + x_len  # the next break; a start when a word follows
+            y_in = y.clamp(max=seq - 1)
+            y_len = length[rows, y_in]
+            grow = (
+                grow & (step < want) & (y < seq) & start[rows, y_in]
+                & (anchor_of[rows, y_in] == 0) & (m + t + y_len <= n)
+            )
+            if not bool(grow.any()):
+                break
+            anchor_of[rows, y_in] = torch.where(
+                grow, mark, anchor_of[rows, y_in]
+            )
+            t = t + torch.where(grow, y_len, zero)
+            x = torch.where(grow, y_in, x)
+            x_len = torch.where(grow, y_len, x_len)
+        m = m + t
+        if bool((m >= n).all()):
+            break
+    mark = anchor_of.gather(1, head)
+    selected = cand & (mark != 0)
+    span_w1 = w1.gather(1, (mark - 1).clamp(min=0))
+    return _mlm_mask_outputs(
+        ids, token_type, attention_mask, selected, span_w1, w2, max_pred,
         vocab_size, mask_token, t_keep, t_rand,
     )
 

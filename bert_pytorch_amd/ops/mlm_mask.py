@@ -22,6 +22,12 @@ is 1 and ``j - 1`` is a candidate; the words are visited in ascending
 of it, when it still fits into ``n``, until ``n`` is reached
 (docs/KERNELS.md has the full definition).
 
+With a ``span_table`` as well (``mlm_span_table``) the selection is by
+spans of whole words: a word that is taken grows over the words that
+follow it, up to a length drawn from ``w3`` of its first position, while
+they are free, adjacent and fit into ``n``; one keep / random / mask
+decision, the anchor's, holds for the whole span.
+
 Nothing depends on the batch a sample sits in, on the worker that read
 it or on the world size, and nothing is read back to the host. No
 autograd: every tensor is an integer.
@@ -71,6 +77,26 @@ def mlm_count_table(
     )
 
 
+def mlm_span_table(p: float, max_len: int) -> torch.Tensor:
+    """int64 [max_len]: the clipped geometric law of the span length in
+    units of 2^-32, ``int(F(k) * 2**32)`` for ``k = 1..max_len`` with
+    ``F(k) = (1 - (1-p)**k) / (1 - (1-p)**max_len)`` (SpanBERT's law,
+    renormalised after clipping), the last entry forced to ``2**32``, in
+    Python's own arithmetic. A word draws ``L = 1 + #{k < max_len : w3 >=
+    table[k-1]}``."""
+    if not (0 < p <= 1):
+        raise ValueError(f"span geometric p must be in (0, 1], got {p}")
+    if not (1 <= max_len <= 32):
+        raise ValueError(f"span max length must be in [1, 32], got {max_len}")
+    norm = 1 - (1 - p) ** max_len
+    table = [
+        int((1 - (1 - p) ** k) / norm * (1 << 32))
+        for k in range(1, max_len + 1)
+    ]
+    table[-1] = 1 << 32
+    return torch.tensor(table, dtype=torch.int64)
+
+
 def _signed64(value: int) -> int:
     value &= 0xFFFFFFFFFFFFFFFF
     return value - (1 << 64) if value >= 1 << 63 else value
@@ -91,6 +117,7 @@ def mlm_mask(
     t_rand: int,
     dense_labels: bool = False,
     word_continues: Optional[torch.Tensor] = None,
+    span_table: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
            torch.Tensor, Optional[torch.Tensor]]:
     """input_ids int32 [B,S], special int32 [B,3] (or [B,2]: the last
@@ -106,8 +133,14 @@ def mlm_mask(
 
     ``word_continues`` (uint8 [vocab_size], 1 where a vocabulary entry
     continues a word; ``data.tokenization.word_continuation_table``)
-    switches to whole-word masking, see above.
+    switches to whole-word masking, see above. ``span_table`` (int64
+    [Lmax], ``mlm_span_table``) on top of it switches to span masking.
     """
+    if span_table is not None and word_continues is None:
+        raise ValueError(
+            "span_table needs word_continues: spans are made of whole words "
+            "(an all-zero table gives token spans)"
+        )
     if input_ids.dim() != 2:
         raise ValueError("input_ids must be [B, S]")
     if special.dim() != 2 or special.shape[1] not in (2, 3):
@@ -115,7 +148,7 @@ def mlm_mask(
     if special.shape[1] == 2:
         special = torch.cat([special, special[:, 1:]], dim=1)
     if use_native(input_ids):
-        # spelled out twice: on the hot path a call costs less than building
+        # spelled out per entry point: on the hot path a call costs less than building
         # and unpacking argument tuples
         if word_continues is None:
             out = extension().mlm_mask(
@@ -123,11 +156,18 @@ def mlm_mask(
                 _signed64(seed), epoch & 0xFFFFFFFF, max_pred, vocab_size,
                 mask_token, t_keep, t_rand, dense_labels,
             )
-        else:
+        elif span_table is None:
             out = extension().mlm_mask_whole_word(
                 input_ids, special.contiguous(), sample_index, count_table,
                 word_continues, _signed64(seed), epoch & 0xFFFFFFFF, max_pred,
                 vocab_size, mask_token, t_keep, t_rand, dense_labels,
+            )
+        else:
+            out = extension().mlm_mask_span(
+                input_ids, special.contiguous(), sample_index, count_table,
+                word_continues, span_table, _signed64(seed),
+                epoch & 0xFFFFFFFF, max_pred, vocab_size, mask_token, t_keep,
+                t_rand, dense_labels,
             )
     else:
         seq = input_ids.shape[1]
@@ -152,5 +192,24 @@ def mlm_mask(
                     f"device of input_ids, got {word_continues.dtype} "
                     f"{tuple(word_continues.shape)} on {word_continues.device}"
                 )
-            out = _reference.mlm_mask_whole_word(*head, word_continues, *tail)
+            if span_table is None:
+                out = _reference.mlm_mask_whole_word(
+                    *head, word_continues, *tail
+                )
+            else:
+                if (
+                    span_table.device != input_ids.device
+                    or span_table.dtype != torch.int64
+                    or span_table.dim() != 1
+                    or not 1 <= span_table.numel() <= 32
+                ):
+                    raise ValueError(
+                        "span_table must be int64 [Lmax], 1 <= Lmax <= 32, "
+                        "on the device of input_ids, got "
+                        f"{span_table.dtype} {tuple(span_table.shape)} on "
+                        f"{span_table.device}"
+                    )
+                out = _reference.mlm_mask_span(
+                    *head, word_continues, span_table, *tail
+                )
     return (*out[:5], out[5] if dense_labels else None)

@@ -70,6 +70,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("epoch"), py::arg("max_pred"), py::arg("vocab_size"),
         py::arg("mask_token"), py::arg("t_keep"), py::arg("t_rand"),
         py::arg("dense_labels") = false);
+  m.def("mlm_mask_span", &bpa::mlm_mask_span,
+        "mlm_mask with spans of whole words from a span-length table",
+        py::arg("input_ids"), py::arg("special"), py::arg("sample_index"),
+        py::arg("count_table"), py::arg("word_continues"),
+        py::arg("span_table"), py::arg("seed"), py::arg("epoch"),
+        py::arg("max_pred"), py::arg("vocab_size"), py::arg("mask_token"),
+        py::arg("t_keep"), py::arg("t_rand"), py::arg("dense_labels") = false);
   m.def("multi_tensor_l2norm_sq", &bpa::multi_tensor_l2norm_sq);
   m.def("multi_tensor_clip_scale", &bpa::multi_tensor_clip_scale);
   m.def("fused_lamb", &bpa::fused_lamb);

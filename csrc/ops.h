@@ -149,6 +149,15 @@ std::vector<torch::Tensor> mlm_mask_whole_word(
     torch::Tensor count_table, torch::Tensor word_continues, int64_t seed,
     int64_t epoch, int64_t max_pred, int64_t vocab_size, int64_t mask_token,
     int64_t t_keep, int64_t t_rand, bool dense_labels);
+// The same with span masking: span_table i64 [Lmax <= 32] holds the clipped
+// geometric law of the span length in units of 2^-32; a taken word grows over
+// the words that follow it and the span shares one keep/random/mask decision.
+std::vector<torch::Tensor> mlm_mask_span(
+    torch::Tensor input_ids, torch::Tensor special, torch::Tensor sample_index,
+    torch::Tensor count_table, torch::Tensor word_continues,
+    torch::Tensor span_table, int64_t seed, int64_t epoch, int64_t max_pred,
+    int64_t vocab_size, int64_t mask_token, int64_t t_keep, int64_t t_rand,
+    bool dense_labels);
 torch::Tensor multi_tensor_l2norm_sq(std::vector<torch::Tensor> tensors);
 void multi_tensor_clip_scale(std::vector<torch::Tensor> grads,
                              torch::Tensor gnorm_sq, double max_norm);

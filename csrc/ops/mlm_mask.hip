@@ -7,29 +7,33 @@
 // counter (j, epoch, lo32(index), hi32(index) | 2^31) under the key `seed`,
 // the n candidates with the smallest (w0 << 32 | j) are selected, and w1 / w2
 // decide keep / random token / mask token. docs/KERNELS.md has the full
-// definition; tests/mlm_mask_spec.py holds the numpy and plain-Python twins
-// the kernel is bit-equal to.
+// definition; tests/mlm_mask_spec.py and tests/mlm_span_spec.py hold the
+// numpy and plain-Python twins the kernel is bit-equal to.
 //
-// One row kernel, mlm_mask_row_kernel<WHOLE_WORD>: one workgroup of 256
+// One row kernel, mlm_mask_row_kernel<MODE>: one workgroup of 256
 // threads per row. Position j belongs to thread j % 256 in every phase, so
 // what a position draws stays in that thread's registers, and a wave's
 // ballot is the 64-bit word j / 64 of a row-wide bit mask in LDS. Header,
 // draw, the count-smaller rank, the selected bits, the substitution, the
 // [B,S] stores and a selected position's index among the row's selected
-// (popcounts over the bit mask) are the same code for both instantiations.
+// (popcounts over the bit mask) are the same code for every instantiation.
 // The template switch changes two things:
 //
 //   * which candidates are selected. Token-level: the ones of rank < n.
 //     Whole words: a uint8 [vocab_size] table of continuation pieces groups
 //     the candidates into words, the words are ordered by the key of their
 //     first position and fill the budget greedily, whole words only.
+//     Spans: the same words in the same order, but a word that is taken
+//     grows over the words that follow it, up to a length drawn from w3 and
+//     a host-built table, and the whole span shares the anchor's keep /
+//     random / mask decision.
 //   * where a row's masked tokens go. Token-level: a row's count is a
 //     function of its specials, so every block recomputes its first slot
 //     from the `special` entries of the rows before it (three integers and a
 //     table lookup per row) and stores to `positions` / `gathered` directly;
 //     the last block fills the unused tail of the slot budget. One launch.
-//     Whole words: the count is known only after the selection, so the row
-//     kernel writes the row's count and a compact list, and
+//     Whole words and spans: the count is known only after the selection,
+//     so the row kernel writes the row's count and a compact list, and
 //     mlm_mask_scatter_kernel, a second launch on the same stream, sums the
 //     counts of the rows before its own, moves the lists to their slots and
 //     fills the tail.
@@ -117,22 +121,32 @@ __device__ __forceinline__ int last_set_upto(const uint64_t* bits, int j) {
   return m != 0 ? (w << 6) + 63 - __builtin_clzll(m) : -1;
 }
 
-// WHOLE_WORD reads word_continues and writes row_count / row_pos / row_label;
-// token-level reads `special` of the rows before and writes positions /
-// gathered. The pointers of the other instantiation are never touched.
-template <bool WHOLE_WORD>
+enum class MaskMode { kToken, kWholeWord, kSpan };
+
+// decision of a span, the byte its words carry in word_sel
+constexpr uint32_t kSpanKeep = 1, kSpanRandom = 2, kSpanMask = 3;
+
+// Whole words and spans read word_continues and write row_count / row_pos /
+// row_label; token-level reads `special` of the rows before and writes
+// positions / gathered. Only spans read span_table (span_max entries). The
+// pointers of the other instantiations are never touched.
+template <MaskMode MODE>
 __global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
     const int32_t* __restrict__ ids, const int32_t* __restrict__ special,
     const int64_t* __restrict__ sample_index,
     const int32_t* __restrict__ table,
-    const uint8_t* __restrict__ word_continues, int64_t* __restrict__ out_ids,
-    int64_t* __restrict__ out_tt, int64_t* __restrict__ out_am,
+    const uint8_t* __restrict__ word_continues,
+    const int64_t* __restrict__ span_table, int span_max,
+    int64_t* __restrict__ out_ids, int64_t* __restrict__ out_tt,
+    int64_t* __restrict__ out_am,
     int64_t* __restrict__ dense,  // may be null
     int64_t* __restrict__ positions, int64_t* __restrict__ gathered,
     int32_t* __restrict__ row_count, int32_t* __restrict__ row_pos,
     int32_t* __restrict__ row_label, int B, int S, int max_pred, uint64_t seed,
     uint32_t epoch, uint32_t vocab_size, int64_t mask_token, uint64_t t_keep,
     uint64_t t_keep_rand) {
+  constexpr bool WHOLE_WORD = MODE != MaskMode::kToken;  // grouped into words
+  constexpr bool SPAN = MODE == MaskMode::kSpan;
   __shared__ uint64_t keys[kMaskMaxS];
   __shared__ uint64_t sel_bits[kMaskWords];
 
@@ -164,6 +178,8 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
 
   int32_t id_r[kMaskPerThread];
   uint32_t w1_r[kMaskPerThread], w2_r[kMaskPerThread];
+  uint32_t w3_r[kMaskPerThread];    // spans only
+  uint32_t code_r[kMaskPerThread];  // spans only: the span's decision
   bool cand_r[kMaskPerThread], sel_r[kMaskPerThread];
 
   // draw: candidates get their sort key, everything else the maximum
@@ -179,6 +195,7 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
       key = (static_cast<uint64_t>(w[0]) << 32) | static_cast<uint32_t>(j);
       w1_r[k] = w[1];
       w2_r[k] = w[2];
+      if constexpr (SPAN) w3_r[k] = w[3];
     }
     id_r[k] = j < S ? ids[row + j] : 0;
     cand_r[k] = cand;
@@ -215,14 +232,27 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
     __syncthreads();
 
     // a word's length is the distance to the next break (position `last`
-    // is one). The words go to `order` by the rank of their key.
+    // is one). The words go to `order` by the rank of their key. A span
+    // anchor adds its decision (bits 10-11) and the words it may still
+    // append (bits 26-30): one for every table entry its w3 reaches.
 #pragma unroll
     for (int k = 0; k < kMaskPerThread; ++k) {
       const int j = k * kMaskThreads + tid;
       if (start_r[k] && n > 0) {
         const int len = next_set_after(break_bits, j) - j;
-        order[count_smaller(keys, S, keys[j])] =
+        uint32_t entry =
             static_cast<uint32_t>(j) | static_cast<uint32_t>(len) << 16;
+        if constexpr (SPAN) {
+          const uint64_t w1 = w1_r[k], w3 = w3_r[k];
+          uint32_t more = 0;
+          for (int i = 0; i < span_max - 1; ++i)  // i < span_max: in the table
+            more += w3 >= static_cast<uint64_t>(span_table[i]) ? 1 : 0;
+          const uint32_t code = w1 < t_keep        ? kSpanKeep
+                                : w1 < t_keep_rand ? kSpanRandom
+                                                   : kSpanMask;
+          entry |= code << 10 | more << 26;  // j, len < 1024; more < 32
+        }
+        order[count_smaller(keys, S, keys[j])] = entry;
       }
     }
     __syncthreads();
@@ -238,6 +268,51 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
       for (int c = 0; c < words && m < n; c += WAVE_SIZE) {
         const bool valid = c + lane < words;
         const uint32_t entry = valid ? order[c + lane] : 0;
+        if constexpr (SPAN) {
+          // Taking a span selects the words it grows over, so the whole-word
+          // shortcut below does not hold: after every span the pending lanes
+          // test again whether their word is still free and still fits. The
+          // span itself is walked by all lanes alike (every value is
+          // wave-uniform, every lane stores the same bytes), so a lane reads
+          // back what it stored itself and no lane waits for another.
+          const int first = static_cast<int>(entry & 0x3FFu);
+          const int len = static_cast<int>(entry >> 16 & 0x3FFu);
+          uint64_t pending = ~uint64_t{0};
+          while (true) {
+            const uint64_t fits =
+                __ballot(valid && len <= n - m && word_sel[first] == 0) &
+                pending;
+            if (fits == 0) break;
+            const int pick = __builtin_ctzll(fits);
+            const uint32_t anchor = static_cast<uint32_t>(
+                __builtin_amdgcn_readlane(static_cast<int>(entry), pick));
+            const uint8_t code = static_cast<uint8_t>(anchor >> 10 & 3u);
+            const int more = static_cast<int>(anchor >> 26);
+            int x = static_cast<int>(anchor & 0x3FFu);  // the span's last word
+            int xlen = static_cast<int>(anchor >> 16 & 0x3FFu);
+            int t = xlen;
+            word_sel[x] = code;
+            for (int i = 0; i < more; ++i) {
+              // the word that starts where x ends, if one does: a special or
+              // `last` is no start. y <= last < S; checked before it indexes.
+              // The three LDS reads do not depend on each other: one round
+              // trip per step, not three
+              const int y = x + xlen;
+              if (y >= S) break;
+              const bool starts = (start_bits[y >> 6] >> (y & 63) & 1) != 0;
+              const bool taken = word_sel[y] != 0;
+              const int ylen = next_set_after(break_bits, y) - y;
+              if (!starts || taken || m + t + ylen > n) break;
+              word_sel[y] = code;
+              t += ylen;
+              x = y;
+              xlen = ylen;
+            }
+            m += t;
+            pending = pick == 63 ? 0 : ~uint64_t{0} << (pick + 1);
+          }
+          continue;
+        }
         const int len = static_cast<int>(entry >> 16);
         bool take = false;
         uint64_t pending = ~uint64_t{0};
@@ -254,16 +329,18 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
     }
     __syncthreads();
 
-    // a candidate is selected with the word it belongs to
+    // a candidate is selected with the word it belongs to (and takes the
+    // decision of the span that word is in)
 #pragma unroll
     for (int k = 0; k < kMaskPerThread; ++k) {
       const int j = k * kMaskThreads + tid;
-      bool sel = false;
+      uint8_t mark = 0;
       if (cand_r[k]) {
         const int head = last_set_upto(start_bits, j);
-        sel = head >= 0 && word_sel[head] != 0;
+        if (head >= 0) mark = word_sel[head];
       }
-      sel_r[k] = sel;
+      sel_r[k] = mark != 0;
+      if constexpr (SPAN) code_r[k] = mark;
     }
   } else {
     __syncthreads();
@@ -294,9 +371,9 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_row_kernel(
     if (sel_r[k]) {
       label = id;
       const uint64_t w1 = w1_r[k];
-      if (w1 < t_keep) {
+      if (SPAN ? code_r[k] == kSpanKeep : w1 < t_keep) {
         // keep the original token
-      } else if (w1 < t_keep_rand) {
+      } else if (SPAN ? code_r[k] == kSpanRandom : w1 < t_keep_rand) {
         id = static_cast<int64_t>(
             (static_cast<uint64_t>(w2_r[k]) * (vocab_size - 1)) >> 32);
       } else {
@@ -354,13 +431,14 @@ __global__ __launch_bounds__(kMaskThreads) void mlm_mask_scatter_kernel(
 
 // Checks the arguments, allocates {masked_ids, token_type_ids,
 // attention_mask, positions, gathered_labels (, dense labels)} and launches:
-// whole words when `word_continues` is given, token-level otherwise.
+// whole words when `word_continues` is given, spans of whole words when
+// `span_table` is given as well, token-level otherwise.
 std::vector<torch::Tensor> mlm_mask_launch(
     const torch::Tensor& input_ids, const torch::Tensor& special,
     const torch::Tensor& sample_index, const torch::Tensor& count_table,
-    const torch::Tensor* word_continues, int64_t seed, int64_t epoch,
-    int64_t max_pred, int64_t vocab_size, int64_t mask_token, int64_t t_keep,
-    int64_t t_rand, bool dense_labels) {
+    const torch::Tensor* word_continues, const torch::Tensor* span_table,
+    int64_t seed, int64_t epoch, int64_t max_pred, int64_t vocab_size,
+    int64_t mask_token, int64_t t_keep, int64_t t_rand, bool dense_labels) {
   TORCH_CHECK(input_ids.is_cuda() && input_ids.dim() == 2 &&
                   input_ids.scalar_type() == torch::kInt32,
               "mlm_mask: input_ids must be a 2D int32 GPU tensor, got ",
@@ -413,6 +491,17 @@ std::vector<torch::Tensor> mlm_mask_launch(
                 vocab_size, "] on the device of input_ids, got ",
                 word_continues->scalar_type(), " ", word_continues->sizes());
   }
+  if (span_table != nullptr) {
+    TORCH_CHECK(word_continues != nullptr,
+                "mlm_mask: span_table needs word_continues");
+    TORCH_CHECK(span_table->device() == input_ids.device() &&
+                    span_table->scalar_type() == torch::kInt64 &&
+                    span_table->dim() == 1 && span_table->size(0) >= 1 &&
+                    span_table->size(0) <= 32 && span_table->is_contiguous(),
+                "mlm_mask: span_table must be contiguous int64 [Lmax], 1 <= "
+                "Lmax <= 32, on the device of input_ids, got ",
+                span_table->scalar_type(), " ", span_table->sizes());
+  }
 
   auto opts = input_ids.options().dtype(torch::kInt64);
   std::vector<torch::Tensor> out = {
@@ -436,14 +525,17 @@ std::vector<torch::Tensor> mlm_mask_launch(
 
   auto stream = at::hip::getCurrentHIPStream();
   const dim3 grid(static_cast<uint32_t>(B)), block(kMaskThreads);
-  const auto row_kernel = word_continues != nullptr
-                              ? mlm_mask_row_kernel<true>
-                              : mlm_mask_row_kernel<false>;
+  const auto row_kernel =
+      span_table != nullptr       ? mlm_mask_row_kernel<MaskMode::kSpan>
+      : word_continues != nullptr ? mlm_mask_row_kernel<MaskMode::kWholeWord>
+                                  : mlm_mask_row_kernel<MaskMode::kToken>;
   hipLaunchKernelGGL(
       row_kernel, grid, block, 0, stream, input_ids.data_ptr<int32_t>(),
       special.data_ptr<int32_t>(), sample_index.data_ptr<int64_t>(),
       count_table.data_ptr<int32_t>(),
       word_continues != nullptr ? word_continues->data_ptr<uint8_t>() : nullptr,
+      span_table != nullptr ? span_table->data_ptr<int64_t>() : nullptr,
+      span_table != nullptr ? static_cast<int>(span_table->size(0)) : 0,
       out[0].data_ptr<int64_t>(), out[1].data_ptr<int64_t>(),
       out[2].data_ptr<int64_t>(),
       dense_labels ? out[5].data_ptr<int64_t>() : nullptr,
@@ -475,7 +567,7 @@ std::vector<torch::Tensor> mlm_mask(torch::Tensor input_ids,
                                     int64_t t_keep, int64_t t_rand,
                                     bool dense_labels) {
   return mlm_mask_launch(input_ids, special, sample_index, count_table, nullptr,
-                         seed, epoch, max_pred, vocab_size, mask_token, t_keep,
+                         nullptr, seed, epoch, max_pred, vocab_size, mask_token, t_keep,
                          t_rand, dense_labels);
 }
 
@@ -485,8 +577,19 @@ std::vector<torch::Tensor> mlm_mask_whole_word(
     int64_t epoch, int64_t max_pred, int64_t vocab_size, int64_t mask_token,
     int64_t t_keep, int64_t t_rand, bool dense_labels) {
   return mlm_mask_launch(input_ids, special, sample_index, count_table,
-                         &word_continues, seed, epoch, max_pred, vocab_size,
-                         mask_token, t_keep, t_rand, dense_labels);
+                         &word_continues, nullptr, seed, epoch, max_pred,
+                         vocab_size, mask_token, t_keep, t_rand, dense_labels);
+}
+
+std::vector<torch::Tensor> mlm_mask_span(
+    torch::Tensor input_ids, torch::Tensor special, torch::Tensor sample_index,
+    torch::Tensor count_table, torch::Tensor word_continues,
+    torch::Tensor span_table, int64_t seed, int64_t epoch, int64_t max_pred,
+    int64_t vocab_size, int64_t mask_token, int64_t t_keep, int64_t t_rand,
+    bool dense_labels) {
+  return mlm_mask_launch(input_ids, special, sample_index, count_table,
+                         &word_continues, &span_table, seed, epoch, max_pred,
+                         vocab_size, mask_token, t_keep, t_rand, dense_labels);
 }
 
 }  // namespace bpa

@@ -110,6 +110,20 @@ def parse_arguments(args=None) -> argparse.Namespace:
                              "unmasked shards; works with and without "
                              "--device_masking; evaluation keeps its static "
                              "token-level masks")
+    parser.add_argument("--span_masking", action="store_true",
+                        help="mask spans of consecutive whole words in the "
+                             "training batches (SpanBERT): span lengths "
+                             "follow a clipped geometric law and a span "
+                             "shares one keep/random/[MASK] decision; needs "
+                             "--vocab_file and unmasked shards; works with "
+                             "and without --device_masking; implies "
+                             "--whole_word_masking; evaluation keeps its "
+                             "static token-level masks")
+    parser.add_argument("--span_max_length", type=int, default=10,
+                        help="--span_masking: longest span, in words (1-32)")
+    parser.add_argument("--span_geometric_p", type=float, default=0.2,
+                        help="--span_masking: parameter of the geometric "
+                             "law of the span length, in (0, 1]")
     parser.add_argument("--vocab_file", type=str, default=None)
     parser.add_argument("--mask_token_index", type=int, default=None)
     parser.add_argument("--vocab_pad_multiple", type=int, default=64,
@@ -145,8 +159,27 @@ def parse_arguments(args=None) -> argparse.Namespace:
     # bool-ish JSON values
     for key in ("fp16", "bf16", "bf16_weights", "kfac", "disable_progress_bar",
                 "checkpoint_activations", "unpad", "device_masking",
-                "whole_word_masking"):
+                "whole_word_masking", "span_masking"):
         setattr(ns, key, bool(getattr(ns, key)))
+    if ns.span_masking:
+        if not ns.vocab_file:
+            raise ValueError(
+                "--span_masking needs --vocab_file: spans are made of whole "
+                "words, and which vocabulary entries continue a word is "
+                "read from the vocabulary. Give the vocabulary the shards "
+                "were encoded with, or drop the flag."
+            )
+        if not 1 <= ns.span_max_length <= 32:
+            raise ValueError(
+                f"--span_max_length must be in [1, 32], got "
+                f"{ns.span_max_length}"
+            )
+        if not 0 < ns.span_geometric_p <= 1:
+            raise ValueError(
+                f"--span_geometric_p must be in (0, 1], got "
+                f"{ns.span_geometric_p}"
+            )
+        ns.whole_word_masking = True  # spans are spans of whole words
     if ns.whole_word_masking and not ns.vocab_file:
         raise ValueError(
             "--whole_word_masking needs --vocab_file: which vocabulary "
@@ -352,9 +385,11 @@ def _word_continues(args, vocab_size):
     if not args.whole_word_masking:
         return None
     if not os.path.isfile(args.vocab_file):
+        flag = "--whole_word_masking"
+        if args.span_masking:
+            flag = "--span_masking"
         raise ValueError(
-            f"--whole_word_masking: --vocab_file {args.vocab_file} does not "
-            "exist"
+            f"{flag}: --vocab_file {args.vocab_file} does not exist"
         )
     from bert_pytorch_amd.data.tokenization import word_continuation_table  # noqa: PLC0415
 
@@ -379,6 +414,9 @@ def prepare_dataset(args, resume_state):
         device_masking=args.device_masking,
         whole_word_masking=whole_word,
         word_continues=_word_continues(args, vocab_size) if whole_word else None,
+        span_masking=args.span_masking and whole_word,
+        span_max_length=args.span_max_length,
+        span_geometric_p=args.span_geometric_p,
     )
     sampler = DistributedSampler(
         dataset, comm.get_world_size(), rank=comm.get_rank(), seed=args.seed
@@ -410,6 +448,8 @@ def prepare_masker(args):
         masked_lm_prob=args.masked_token_fraction,
         vocab_size=vocab_size,
         word_continues=_word_continues(args, vocab_size),
+        span_max_length=args.span_max_length if args.span_masking else None,
+        span_geometric_p=args.span_geometric_p,
     )
 
 
